@@ -3,6 +3,15 @@ config — 4D rolling spline coupling flow, K=16 knots, 4 couplings, hidden
 (128, 128), Normal latent, batch 2^20 per GPU — through the fused HIP kernel.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline figure, its roofline from the timed launches and the NLL of
+the last step).  ``--dump-outputs DIR`` also writes what the last timed step
+computed as DIR/<name>.npy.  ``--full`` adds every other leg to the same
+line: the K1 spline-kernel roofline, the CPU baseline with the parity
+against the oracle, the other BASELINE configs and, for cfg1, the
+resident-batch and sample rates (each leg has its ``--no-...`` switch).
 
 One process per GPU, no torch: ``--gpus N`` (N>1) spawns N fresh ranks
 itself (zenflow_amd.launch.spawn) unless the env already holds a launch
@@ -295,6 +304,27 @@ def sample_rows(N, n=4096):
     return np.arange(0, N, max(1, N // n))[:n]
 
 
+DUMP_BUDGET_BYTES = 32 << 20  # per run, all arrays and ranks together
+
+
+def dump_outputs(directory, arrays, rank, world):
+    """Write the last timed step's outputs as <directory>/<name>.npy
+    (<name>_rank<r>.npy when there is more than one rank), float32 or
+    float64.  An array over its share of DUMP_BUDGET_BYTES is cut to a fixed
+    seeded sample of its rows, in row order, the same from run to run."""
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // (world * len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            n = max(1, budget // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(20240 + rank).choice(a.shape[0], n, replace=False))
+            a = a[rows]
+        np.save(directory / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
+
+
 def logprob_parity(spec, variables, x, c, lp, rows):
     """GPU log_prob on sampled rows vs the oracle (tests/test_gpu_flow.py's
     bars): north_star's unwidened strict error against the fp32 oracle on all
@@ -430,16 +460,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="cfg2", choices=sorted(WORKLOADS))
     ap.add_argument("--rows-log2", type=int, default=None, help="rows per GPU = 2^k (default 20; cfg1: 12)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: K1 spline-kernel roofline, CPU baseline and "
+                         "parity, the other BASELINE configs, cfg1's resident / sample rates")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
     ap.add_argument("--cpu-budget", type=float, default=24.0)
-    ap.add_argument("--no-spline-kernel", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs (rank 0, N=1)")
+    ap.add_argument("--no-spline-kernel", action="store_true", help="with --full: skip the K1 spline-kernel roofline")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the other BASELINE configs (rank 0, N=1)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch and rendezvous only: rank 0 prints the run's config, no GPU is touched")
     ap.add_argument("--force-rccl", action="store_true", help="RCCL all-reduce even at world size 1 (plumbing check)")
     ap.add_argument("--serial-allreduce", action="store_true",
                     help="NLL all-reduce on the compute stream after every step (no overlap)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start one fresh process per GPU (before this
@@ -490,13 +528,15 @@ def main():
         comm = RcclCommunicator(rank, world, bcast, force=args.force_rccl)
     dp = DataParallelLogProb(DeviceLogProbStep(prog, N), comm, overlap=not args.serial_allreduce)
 
+    host_out = {}  # apply mode: the host array the last step returned
+
     def step(ev=None):
         if mode == "log_prob":
             dp.step(xd, cd, out, ev)
         elif mode == "apply":  # Flow.__call__ through apply: host x in, host log_prob out
             if ev is not None:
                 ev[0].record()
-            flow.apply(variables, x, c)
+            host_out["log_prob"] = flow.apply(variables, x, c)
             if ev is not None:
                 ev[1].record()
         elif mode == "sample":
@@ -535,6 +575,16 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     total = N * world * args.steps
     value = total / elapsed
+    nll = dp.nll(N * world) if mode == "log_prob" else None
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step
+        if mode == "log_prob":
+            dumped = {"log_prob": out.numpy(), "nll": np.array([nll], np.float64)}
+        elif mode == "apply":
+            dumped = {"log_prob": host_out["log_prob"]}
+        else:
+            dumped = {"x": out.numpy()}
+        dump_outputs(args.dump_outputs, dumped, rank, world)
 
     fps = flops_per_sample(name)
     achieved = fps * N / (kavg * 1e-3) / 1e12
@@ -590,9 +640,9 @@ def main():
         },
     }
     if mode == "log_prob":
-        result["nll"] = dp.nll(N * world)
+        result["nll"] = nll
         result["config"]["communicator_ranks"] = comm.world if comm is not None else 1
-    if mode == "apply":
+    if mode == "apply" and args.full:
         # the same batch resident in HBM (fused kernel + NLL reduce only), and
         # Flow.sample through apply (latent drawn on the device, host out)
         rate = {}
@@ -614,11 +664,11 @@ def main():
         result["apply_path"] = {"log_prob_apply_samples_per_s": value, **{k + "_samples_per_s": v for k, v in rate.items()},
                                 "note": "value = Flow.apply(variables, x_host) per step: host->device copy, fused "
                                         "kernel, device->host copy and Python dispatch; cached device program"}
-    if not args.no_spline_kernel and rank == 0:
+    if args.full and not args.no_spline_kernel and rank == 0:
         result["spline_kernel"] = spline_kernel_roofline(N, 2, K, args.steps)
         if K != 32:  # K1 at 32 knots too (the two-lanes-per-item kernel)
             result["spline_kernel_k32"] = spline_kernel_roofline(N, 2, 32, args.steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         spec = oracle_spec(name)
         if mode in ("log_prob", "apply"):
             cb, outs = cpu_baseline(spec, variables, x, c, args.cpu_budget)
@@ -644,7 +694,7 @@ def main():
                                 "fp64_subset": logprob_parity(spec, variables, x, c, lp, sample_rows(N, 8192))}
             result["cpu_baseline"] = cb
             result["speedup_vs_cpu"] = value / cb["value"]
-    if rank == 0 and world == 1 and name == "cfg2" and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and name == "cfg2" and not args.no_configs:
         # every other BASELINE config with its parity, in the same driver-run record
         result["configs"] = config_block(["cfg3", "cfg3s", "cfg4", "cfg5"], min(args.steps, 10), 2)
     if rank == 0:

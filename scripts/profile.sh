@@ -11,7 +11,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 REPO=$(pwd)
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-spline-kernel ${BENCH_ARGS:-}"
+B="python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-spline-kernel ${BENCH_ARGS:-}"
 run() {  # run <name> <timeout> <args...>
   local name=$1 tmo=$2; shift 2
   echo "=== $name" | tee -a gpurun_out/stages.log

@@ -80,9 +80,11 @@ def test_torchrun_style_env(tmp_path):
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_spawns_ranks(world):
     """`python bench.py --gpus N` with no launcher starts N ranks itself;
-    on this GPU-less host each reaches the no-device error of the product
-    path (no CPU fallback)."""
+    with every GPU masked from the ranks (so the test is the same on a host
+    with GPUs and on one without) each reaches the no-device error of the
+    product path (no CPU fallback)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ZF_RDZV_DIR")}
+    env.update(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
