@@ -396,6 +396,13 @@ struct zf_flow {
   bool x3_oact = false;  // some coupling's activation is not swish
   int x3_aset = 0;       // X3Launch::aset: which non-swish activations the flow uses
   int device = 0;
+  // resident form of the split-MFMA kernel: ZF_X3_RESIDENT at create, the
+  // device's CU count, and the state scratch (rows x (dim + 1) floats, grown
+  // on demand: one call in flight per handle, as the layered path)
+  int x3_res_mode = -1;
+  int ncu = 0;
+  float* d_res_state = nullptr;
+  long long res_floats = 0;
   zf::LayeredFlow* lay = nullptr;  // layered eval path (a hidden width > 256), or null
 };
 
@@ -506,6 +513,7 @@ int zf_flow_create(const zf_flow_desc* desc_in, const float* blob_host, int64_t 
   int x3K = 0;
   // the split-MFMA kernel runs hidden <= 128 padded to 128 (4 tiles)
   const bool x3 = !layered && zf::x3_eligible(desc, F.HP < 128 ? 128 : F.HP, &x3K);
+  h->x3_res_mode = zf::x3_resident_mode();
   if (x3 && F.HP < 128) F.HP = 128;
   const int HP = F.HP, T = HP / 32;
   // Latent constants in fp32, as jax.scipy.stats computes them.
@@ -660,6 +668,8 @@ int zf_flow_create(const zf_flow_desc* desc_in, const float* blob_host, int64_t 
   const bool use_x3 = F.x3_ok != 0;
   int rcd = ZF_OK;
   hipError_t e = hipGetDevice(&h->device);
+  if (e == hipSuccess && use_x3)
+    (void)hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->device);
   if (e == hipSuccess && layered) {
     rcd = zf::layered_create(desc, nat, need, &h->lay);
     if (rcd) {
@@ -690,6 +700,7 @@ int zf_flow_destroy(zf_flow_t* h) {
   if (h->d_desc) (void)hipFree(h->d_desc);
   if (h->d_blob) (void)hipFree(h->d_blob);
   if (h->d_x3) (void)hipFree(h->d_x3);
+  if (h->d_res_state) (void)hipFree(h->d_res_state);
   zf::layered_destroy(h->lay);
   delete h;
   return ZF_OK;
@@ -710,6 +721,11 @@ int64_t zf_flow_workspace_bytes(int64_t N) {
 
 namespace zf {
 namespace {
+
+// Automatic use of the resident form (ZF_X3_RESIDENT unset): from this row
+// count on — the smallest measured size from which it was never the slower
+// form (profiles/resident_rows_sweep.txt: slower at 2^16, even at 2^17-2^18).
+constexpr int64_t kX3ResidentAutoRows = 1 << 19;
 
 template <bool INV>
 int launch_flow(zf_flow* h, int op_begin, int op_end, const float* x, const float* c, float* y,
@@ -737,6 +753,23 @@ int launch_flow(zf_flow* h, int op_begin, int op_end, const float* x, const floa
     a.seed = seed;
     a.gen = gen;
     a.stream = (hipStream_t)stream;
+    // the resident form: forced (ZF_X3_RESIDENT=1) or from kX3ResidentAutoRows rows on
+    if (h->x3_res_mode != 0 && (h->x3_res_mode == 1 || N >= kX3ResidentAutoRows) &&
+        x3_resident_fits(h->desc, a, INV, h->ncu)) {
+      const long long need = ((long long)(N + kTile - 1) / kTile) * kTile * (h->host.D + 1);
+      if (need > h->res_floats) {
+        // a call being captured cannot allocate: it takes the streaming form
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(a.stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+          if (h->d_res_state) (void)hipFree(h->d_res_state);
+          h->d_res_state = nullptr;
+          h->res_floats = 0;
+          ZF_TRY_HIP(hipMalloc(&h->d_res_state, (size_t)need * sizeof(float)));
+          h->res_floats = need;
+        }
+      }
+      if (need <= h->res_floats) a.res_state = h->d_res_state;
+    }
     return launch_flow_x3(a, INV);
   }
   const int64_t grid = (N + kBlockRows - 1) / kBlockRows;

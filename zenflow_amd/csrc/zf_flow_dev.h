@@ -301,6 +301,36 @@ __device__ __forceinline__ float nan_to_num_lp(float lp) {
 // (and zero into the pstride-1 slots after it that are < nparts), or
 // part[slot] when given, so every kernel shape leaves the same
 // ceil(N/128)-entry workspace for reduce.
+// Per-row part of the epilogue: log_prob of this wave's rows (stored when
+// valid), and — want_sum — their fp64 sum, on every lane (rows of the upper
+// lane half and invalid rows count as zero).
+__device__ __forceinline__ double flow_lp_rows(const DevFlow* __restrict__ F, const float* xs, int s, int hh,
+                                               int rot, int D, long long row, bool valid, float ld,
+                                               float* __restrict__ lp_out, bool want_sum) {
+  float lat = 0.f;
+  for (int j = 0; j < D; ++j)
+    lat = lat + latent_logpdf(F->latent, F->lat_c0, F->lat_c1, F->lat_c2, xs[wrap(j + rot, D) * 32 + s]);
+  const float lp = nan_to_num_lp(lat + ld);
+  if (valid && hh == 0) lp_out[row] = lp;
+  double v = 0.0;
+  if (want_sum) {
+    v = (valid && hh == 0) ? (double)lp : 0.0;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  }
+  return v;
+}
+
+// The optional y / log_det outputs of this wave's rows.
+__device__ __forceinline__ void flow_out_rows(const float* xs, int s, int hh, int rot, int D, long long row,
+                                              bool valid, float ld, float* __restrict__ y_out,
+                                              float* __restrict__ ld_out) {
+  if (y_out != nullptr && valid) {
+    for (int j = hh; j < D; j += 2) y_out[row * D + j] = xs[wrap(j + rot, D) * 32 + s];
+  }
+  if (ld_out != nullptr && valid && hh == 0) ld_out[row] = ld;
+}
+
 template <int NW>
 __device__ __forceinline__ void flow_epilogue(const DevFlow* __restrict__ F, const float* xs, int s,
                                               int hh, int lane, int wave, int rot, int D, long long row,
@@ -310,15 +340,8 @@ __device__ __forceinline__ void flow_epilogue(const DevFlow* __restrict__ F, con
                                               float* __restrict__ ld_out, double* s_part,
                                               long long slot = -1) {
   if (lp_out != nullptr) {
-    float lat = 0.f;
-    for (int j = 0; j < D; ++j)
-      lat = lat + latent_logpdf(F->latent, F->lat_c0, F->lat_c1, F->lat_c2, xs[wrap(j + rot, D) * 32 + s]);
-    const float lp = nan_to_num_lp(lat + ld);
-    if (valid && hh == 0) lp_out[row] = lp;
+    const double v = flow_lp_rows(F, xs, s, hh, rot, D, row, valid, ld, lp_out, block_partial != nullptr);
     if (block_partial != nullptr) {
-      double v = (valid && hh == 0) ? (double)lp : 0.0;
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
       if (lane == 0) s_part[wave] = v;
       __syncthreads();
       if (threadIdx.x == 0) {
@@ -333,10 +356,7 @@ __device__ __forceinline__ void flow_epilogue(const DevFlow* __restrict__ F, con
       }
     }
   }
-  if (y_out != nullptr && valid) {
-    for (int j = hh; j < D; j += 2) y_out[row * D + j] = xs[wrap(j + rot, D) * 32 + s];
-  }
-  if (ld_out != nullptr && valid && hh == 0) ld_out[row] = ld;
+  flow_out_rows(xs, s, hh, rot, D, row, valid, ld, y_out, ld_out);
 }
 
 // Host-side entry of the bf16x3 kernel (zf_flow_x3.hip).
@@ -359,9 +379,18 @@ struct X3Launch {
   bool oact;    // some coupling's activation is not swish (f16x2 kernels with act switch)
   int aset;     // oact, f16x2: 2 = only sigmoid/softplus (the _act2 units), 1 = only relu/tanh/gelu/elu/leaky_relu, 0 = both kinds (1 and 0: the full switch)
   int par_bytes;  // DevFlow::x3_par_bytes
+  // resident form (flow_kernel_x3r): the state scratch (null: the streaming
+  // form), blocks (one per CU), 128-row slots per block, LDS bytes of the
+  // largest coupling span
+  float* res_state = nullptr;
+  int res_blocks = 0, res_slots = 0, res_span = 0;
   hipStream_t stream;
 };
 int launch_flow_x3(const X3Launch& a, bool inverse);
+// Resident form: ZF_X3_RESIDENT (0: never, 1: whenever eligible, unset / other: -1, automatic),
+// and whether a call of this shape can run it (fills res_blocks / res_slots / res_span).
+int x3_resident_mode();
+bool x3_resident_fits(const zf_flow_desc& desc, X3Launch& a, bool inverse, int ncu);
 bool x3_eligible(const zf_flow_desc& desc, int HP, int* K);
 // Layered eval path (zf_layered.hip) for shapes the fused kernels cannot hold
 // (a hidden width above 256): op by op over row chunks — BatchNorm, the Dense

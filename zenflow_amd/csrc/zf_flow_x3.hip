@@ -39,6 +39,10 @@ float bf16_f(uint16_t b) {
 int x3_padded_knots(int K);
 int x3_param_of(int jp, int Kp, int K, float* fill);
 
+int x3_last_tiles(int K) { return (3 * K - 1 + 15) / 16; }
+// ONE layout (one transformed dim): 32 parameters per tile
+int x3_last_tiles_one(int K) { return (3 * K - 1 + 31) / 32; }
+
 // One knot count for all couplings and one of the instantiated shapes
 // (launch_flow_x3).
 bool x3_eligible(const zf_flow_desc& desc, int HP, int* K_out) {
@@ -75,6 +79,51 @@ bool x3_eligible(const zf_flow_desc& desc, int HP, int* K_out) {
   const int Kp = x3_padded_knots(K);
   if (HP > 256 || desc.dim > 64 || Kp == 0) return false;
   *K_out = Kp;
+  return true;
+}
+
+// ZF_X3_RESIDENT, read at create like ZF_DISABLE_X3: 0 = never the resident
+// form (flow_kernel_x3r), 1 = whenever the call is eligible, anything else
+// (unset) = automatic, from the measured row count on (zf_flow.hip).
+int x3_resident_mode() {
+  const char* env = std::getenv("ZF_X3_RESIDENT");
+  if (env && env[0] == '0' && env[1] == 0) return 0;
+  if (env && env[0] == '1' && env[1] == 0) return 1;
+  return -1;
+}
+
+// Whether this call can run the resident form on `ncu` CUs, one block each:
+// f16x2 swish at hidden 128 with one streamed hidden layer per coupling and
+// one pair of transformed dims, an NSC in the op range, an instantiated
+// kernel, and the LDS budget: the largest coupling's whole span + one
+// parameter region + 12 waves x 2 state buffers + one fp64 sum per tile of
+// the block <= 160 KiB.  With T = 4: span = 4 x 16 KiB + 4 x TL x 4 KiB
+// (112 KiB at K = 16, two dims), so K = 32 with two dims (160 KiB) never fits.
+bool x3_resident_fits(const zf_flow_desc& desc, X3Launch& a, bool inverse, int ncu) {
+  if (a.NT != 2 || a.T != 4 || a.oact || ncu <= 0 || a.N <= 0) return false;
+  const int dt = desc.dim / 2;
+  if (dt > 2) return false;  // a dim-pair loop (PAIRS)
+  bool in_range = false;
+  for (int i = 0; i < desc.n_ops; ++i) {
+    if (desc.ops[i].kind != ZF_OP_NSC) continue;
+    if (desc.ops[i].n_hidden != 2) return false;
+    if (i >= a.op_begin && i < a.op_end) in_range = true;
+  }
+  if (!in_range) return false;
+  const int TL = dt == 1 ? x3_last_tiles_one(a.K) : x3_last_tiles(a.K);
+  const long long span = 4ll * (2 * 4 * 2 * 1024) + 4ll * (2 * TL * 2 * 1024);
+  const long long nslots = (a.N + 127) / 128;
+  const long long slots = (nslots + ncu - 1) / ncu;
+  if (slots > (1 << 20)) return false;
+  if (x3_res_lds_bytes((size_t)span, a.par_bytes, a.D + a.C, 4 * slots) > 160 * 1024) return false;
+  // instantiated: K = 16 with two transformed dims, forward and inverse
+  // (zf_flow_x3_k16_res.hip).  One transformed dim (cfg4's shape) fits the
+  // budget too but did not beat the streaming form by the A/B margin
+  // (profiles/resident_ab.txt), and K = 8 / 32 were not measured.
+  if (a.K != 16 || dt != 2) return false;
+  a.res_blocks = ncu;
+  a.res_slots = (int)slots;
+  a.res_span = (int)span;
   return true;
 }
 
@@ -127,9 +176,6 @@ int x3_scheme_for(const zf_flow_desc& desc) {
   return x3_scheme() == 3 ? 3 : 2;
 }
 
-int x3_last_tiles(int K) { return (3 * K - 1 + 15) / 16; }
-// ONE layout (one transformed dim): 32 parameters per tile
-int x3_last_tiles_one(int K) { return (3 * K - 1 + 31) / 32; }
 
 int x3_pairs(const zf_flow_desc& desc) { return (desc.dim / 2 + 1) / 2; }
 

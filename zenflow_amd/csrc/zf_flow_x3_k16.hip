@@ -5,9 +5,11 @@
 namespace zf {
 
 int launch_x3_k16_act(const X3Launch& a, bool inverse);
+int launch_x3r_k16(const X3Launch& a, bool inverse);
 
 int launch_x3_k16(const X3Launch& a, bool inverse) {
   if (a.oact) return launch_x3_k16_act(a, inverse);
+  if (a.res_state != nullptr) return launch_x3r_k16(a, inverse);
   return a.NT == 2 ? launch_x3_k<2, 16>(a, inverse) : launch_x3_k<3, 16>(a, inverse);
 }
 

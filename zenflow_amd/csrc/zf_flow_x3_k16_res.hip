@@ -1,0 +1,12 @@
+// Resident form of the split-MFMA fused flow kernel (flow_kernel_x3r,
+// zf_flow_x3_kernel.h), K = 16 knots: swish couplings with two transformed
+// dims, forward and inverse / sample — the shapes that measured faster than
+// the streaming form (profiles/resident_ab.txt).  Every other shape stays on
+// the streaming form (x3_resident_fits).
+#include "zf_flow_x3_kernel.h"
+
+namespace zf {
+
+int launch_x3r_k16(const X3Launch& a, bool inverse) { return launch_x3r<16, false>(a, inverse); }
+
+}  // namespace zf

@@ -34,6 +34,9 @@
 // Eligibility (host, x3_eligible): hidden widths <= 256 (<= 128 padded to
 // 128), one knot count in {8, 16, 32} for all couplings, dim <= 64.
 // Everything else, and ZF_DISABLE_X3=1, runs flow_kernel.
+// Large batches of the shapes x3_resident_fits names run the resident form
+// flow_kernel_x3r below instead: the same per-row code (x3_nsc), coupling-major,
+// with a coupling's whole weight span kept in LDS.
 #pragma once
 #include "zf_flow_dev.h"
 
@@ -549,11 +552,12 @@ __device__ __forceinline__ X3Span make_span(const X3Sc& c, bool has_next) {
 // Issue the DMA of one group into an LDS buffer: 1 KiB pieces (one
 // global_load_lds_dwordx4 per wave: wave-uniform LDS base, lane*16 implied)
 // spread over the block's waves.
-__device__ __forceinline__ void x3_dma(const char* __restrict__ src, char* dst, int pieces, int wave, int lane) {
+__device__ __forceinline__ void x3_dma(const char* __restrict__ src, char* dst, int pieces, int wave, int lane,
+                                       int nw = kX3Waves) {
 #if ZF_X3_ABL == 5  // tuning ablation 5: a quarter of the weight stream (wrong results)
   pieces = (pieces + 3) / 4;
 #endif
-  for (int p = wave; p < pieces; p += kX3Waves)
+  for (int p = wave; p < pieces; p += nw)
     __builtin_amdgcn_global_load_lds((const void*)(src + (p << 10) + lane * 16),
                                      (__attribute__((address_space(3))) void*)(dst + (p << 10)), 16, 0, 0);
 }
@@ -601,6 +605,20 @@ __device__ __forceinline__ void x3_issue_next(const char* __restrict__ x3, const
     pieces = p.span.next_pieces;
   }
   x3_dma(x3 + off, dst, pieces, p.wave, lane);
+}
+
+// After a group step: the double buffer swaps, or (RES) the cursor moves to
+// the next group of the resident span.
+template <bool RES, int BYTES>
+__device__ __forceinline__ void x3_advance(X3Pipe& p) {
+  if constexpr (RES) {
+    p.cur += BYTES;
+  } else {
+    char* const t = p.cur;
+    p.cur = p.nxt;
+    p.nxt = t;
+  }
+  p.g += 1;
 }
 
 // One pipeline step: wait for this wave's DMAs, block barrier (the group in
@@ -824,20 +842,26 @@ __device__ __forceinline__ void x3_valu_tail(std::integer_sequence<int, M...>, f
 // (Q+1, 0)), pinned by scheduling barriers, so the VALU issues between the
 // MFMAs of the wave's own dependent triples instead of after them; the A
 // fragments of the next triple are read one triple ahead.
-template <int T, int NOUT, int Q, bool HASB>
+//
+// RES (the resident form, flow_kernel_x3r): the NSC's whole span is in LDS
+// and p.cur walks it group by group, so the step has no DMA wait, no block
+// barrier, no prefetch and no buffer swap.
+template <int T, int NOUT, int Q, bool HASB, bool RES = false>
 __device__ __forceinline__ void x3_step_slots(const char* __restrict__ x3, X3Pipe& p, floatx16 (&hb)[T],
                                               floatx16 (&acc)[NOUT], int lane, const float* __restrict__ bias,
                                               int hh, halfx8 (&cs)[2], float isc, float us) {
   constexpr int NT = 2;
+  if constexpr (!RES) {
 #ifdef ZF_X3_TRACE
-  const unsigned long long tb0 = X3T_NOW();
+    const unsigned long long tb0 = X3T_NOW();
 #endif
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
 #ifdef ZF_X3_TRACE
-  p.tbar += X3T_NOW() - tb0;
+    p.tbar += X3T_NOW() - tb0;
 #endif
-  x3_issue_next<NT, T>(x3, p, p.nxt, lane);
+    x3_issue_next<NT, T>(x3, p, p.nxt, lane);
+  }
   const char* lb = p.cur + lane * 16;
   halfx8 fr[2][NT];
   load_frag<NT>(lb, fr[0]);
@@ -865,10 +889,7 @@ __device__ __forceinline__ void x3_step_slots(const char* __restrict__ x3, X3Pip
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) acc[o] = x3_finish<NT>(acc[o], us, bias_acc(bias + o * 32, hh));
   }
-  char* const t = p.cur;
-  p.cur = p.nxt;
-  p.nxt = t;
-  p.g += 1;
+  x3_advance<RES, group_bytes<NT>(NOUT)>(p);
 }
 
 // Early per-sample scale (x3_early_scale, f16x2 swish at hidden 128): the
@@ -992,13 +1013,15 @@ __device__ __forceinline__ void x3_valu_tail_last(std::integer_sequence<int, M..
 // finished pre-activations acc * us + bias, and NEXT: tile 0 swished with the
 // next layer's constant cn and cs its k-step-0 split (what the next layer's
 // first x3_step_slots expects of hb[0] / cs).
-template <int T, int NOUT, bool NEXT, int SPT = 0>
+template <int T, int NOUT, bool NEXT, int SPT = 0, bool RES = false>
 __device__ __forceinline__ void x3_step_slots_last(const char* __restrict__ x3, X3Pipe& p, floatx16 (&hb)[T],
                                                    floatx16 (&acc)[NOUT], int lane, const float* __restrict__ bias,
                                                    int hh, halfx8 (&cs)[2], float us, float cn, float& mx) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  x3_issue_next<2, T>(x3, p, p.nxt, lane);
+  if constexpr (!RES) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    x3_issue_next<2, T>(x3, p, p.nxt, lane);
+  }
   const char* lb = p.cur + lane * 16;
   halfx8 fr[2][2];
   load_frag<2>(lb, fr[0]);
@@ -1014,10 +1037,7 @@ __device__ __forceinline__ void x3_step_slots_last(const char* __restrict__ x3, 
                                         csh, bt, bias, hh, us, cn, mx);
   x3_valu_tail_last<T, NOUT, NEXT, SPT>(std::make_integer_sequence<int, (kEnd > kSlots ? kEnd - kSlots : 0)>{}, hb,
                                         acc, cs, s1, tq, s1h, csh, bt, bias, hh, us, cn, mx);
-  char* const t = p.cur;
-  p.cur = p.nxt;
-  p.nxt = t;
-  p.g += 1;
+  x3_advance<RES, group_bytes<2>(NOUT)>(p);
 }
 
 // Fused swish + split (ZF_X3_FUSED): the hi / lo fp16 terms of the exact
@@ -1204,15 +1224,15 @@ __device__ __forceinline__ void x3_layer_pipe(const char* __restrict__ x3, X3Pip
 // x3_step_slots (the layer input's tiles 1..T-1 swished with c in their
 // slots), then x3_step_slots_last (finish; NEXT: the next layer's tile 0
 // swished with cn and split into cs).
-template <int T, int NOUT, bool NEXT, int SPT = 0, int Q = 0>
+template <int T, int NOUT, bool NEXT, int SPT = 0, int Q = 0, bool RES = false>
 __device__ __forceinline__ void x3_layer_early(const char* __restrict__ x3, X3Pipe& p, floatx16 (&hb)[T],
                                                floatx16 (&acc)[NOUT], int lane, const float* __restrict__ bias,
                                                int hh, halfx8 (&cs)[2], float c, float us, float cn, float& mx) {
   if constexpr (Q + 1 < T) {
-    x3_step_slots<T, NOUT, Q, false>(x3, p, hb, acc, lane, nullptr, hh, cs, c, us);
-    x3_layer_early<T, NOUT, NEXT, SPT, Q + 1>(x3, p, hb, acc, lane, bias, hh, cs, c, us, cn, mx);
+    x3_step_slots<T, NOUT, Q, false, RES>(x3, p, hb, acc, lane, nullptr, hh, cs, c, us);
+    x3_layer_early<T, NOUT, NEXT, SPT, Q + 1, RES>(x3, p, hb, acc, lane, bias, hh, cs, c, us, cn, mx);
   } else {
-    x3_step_slots_last<T, NOUT, NEXT, SPT>(x3, p, hb, acc, lane, bias, hh, cs, us, cn, mx);
+    x3_step_slots_last<T, NOUT, NEXT, SPT, RES>(x3, p, hb, acc, lane, bias, hh, cs, us, cn, mx);
   }
 }
 
@@ -1452,6 +1472,599 @@ __device__ __forceinline__ RqsBin x3_bin(float v, const float (&P)[NPV], const K
 template <int T, int K, bool PAIRS>
 constexpr int x3_occupancy() { return (T == 8 || K > 32) ? 1 : (PAIRS || K > 16) ? 2 : 3; }
 
+// Phase-trace / marker hooks of the kernel bodies below (tuning builds only;
+// nothing in the shipped build).  Trace slots: 0 start->first NSC, 1 layer 0,
+// 2 hidden layers, 3 hidden->last transition, 4 last layer, 5 spline,
+// 6 epilogue, 7 barrier waits (inside 2 and 4), 8 total, 9 couplings,
+// 10 other ops.
+#ifdef ZF_X3_TRACE
+struct X3Tr {
+  unsigned long long tacc[kX3TraceSlots];
+  unsigned long long t_last;
+};
+#define X3T(k)                                   \
+  {                                              \
+    const unsigned long long t_ = X3T_NOW();     \
+    tr.tacc[k] += t_ - tr.t_last;                \
+    tr.t_last = t_;                              \
+  }
+#elif defined(ZF_X3_MARK)
+// tuning only: phase markers in the .s for per-phase static instruction counts
+struct X3Tr {};
+#define X3T(k) asm volatile(";ZFMARK " #k)
+#else
+struct X3Tr {};
+#define X3T(k)
+#endif
+#ifdef ZF_X3_MARK
+#define X3M(k) asm volatile(";ZFMARK " #k)
+#else
+#define X3M(k)
+#endif
+
+// One NeuralSplineCoupling (bijectors.py:329-371) on this wave's 32 samples:
+// layer 0 from the LDS parameter region `par`, the streamed layers from the
+// weight groups behind `pipe` (RES: from the resident span), the spline on
+// the transformed dims of the per-wave state `xs`, the log-det into `ld`.
+template <int NT, int K, int T, bool PAIRS, bool ONE, bool INV, bool OACT, int ASET, bool RES>
+__device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const char* __restrict__ x3, X3Pipe& pipe,
+                                       const float* par, float* xs, int rot, int D, int s, int hh, int lane,
+                                       float& ld, X3Tr& tr) {
+  // last-layer tiles per dim pair: 16 parameters per lane half (ONE: 32 of one dim per tile)
+  constexpr int TL = ONE ? (3 * K - 1 + 31) / 32 : (3 * K - 1 + 15) / 16;
+  constexpr int NPV = ONE ? 32 * TL : 16 * TL;  // spline parameters held per lane
+  const int nh = opc.nh, act = opc.act, dt = opc.dt, kw_last = opc.kw_last;
+  // this coupling's knots: a chain may mix knot counts up to the kernel's K
+  // (x3_padded_knots); K - 1 real knots put the idx == K sliver at the
+  // padded knot (rqs_bin_monotone padlast)
+  const KnotConsts kc(opc.kreal);
+  const bool padlast = opc.kreal == K - 1;
+#ifdef ZF_X3_MARK
+  const bool klit = true;  // marker builds: count one x3_bin copy
+#else
+  const bool klit = opc.kreal == K;  // x3_bin: the knot constants as literals
+#endif
+  // hidden biases are consecutive T x 32 blocks after Dense_0's (zf_flow.hip: b[l] = b[0] + l T 32)
+  const long long b_rel = opc.b_rel + T * 32, blast_rel = opc.blast_rel;
+  floatx16 hb[T];
+  // The swish of a layer's output is deferred tile by tile into the next
+  // streamed layer (x3_step, SW) — except before a PAIRS last layer,
+  // which passes over its input once per dim pair.
+  constexpr bool kLastSW = !PAIRS;
+  constexpr bool kPipe = T == 4 && !PAIRS;
+  // f16x2: every layer leaves raw pre-activations; the next streamed
+  // layer scales and swishes them (act_swish) as it goes.
+  // bf16x3 OACT: every tile's activation at the layer end (no switch inside
+  // the group steps)
+#ifndef ZF_X3_EARLY
+#define ZF_X3_EARLY 1
+#endif
+  // f16x2 swish at hidden 128 (one dim pair): scales from bounds (x3_early_scale)
+  constexpr bool kEarly = ZF_X3_EARLY && NT == 2 && !OACT && kPipe;
+  static_assert(!RES || kEarly, "the resident form runs the early-scale slot schedule only");
+  // kEarly: the last layer's width / height tiles leave its last group
+  // step as 2 squareplus (x3_step_slots_last SPT): K / 8 tiles of 16 per
+  // lane half (one dim per half); ONE at K = 16: tile 0 (widths on half 0,
+  // heights on half 1, the kSplitWH layout)
+#ifndef ZF_X3_PRESP
+#define ZF_X3_PRESP 1
+#endif
+  constexpr int kPreSP = (!ZF_X3_PRESP || !kEarly) ? 0 : !ONE ? K / 8 : (K == 16 ? 1 : 0);
+  float umax = 0.f;
+  x3_layer0<T, OACT>(opc, par, xs, rot, D, s, hh, lane, hb, NT == 2 ? 0 : (!OACT && (nh > 1 || kLastSW)) ? 1 : T,
+                     kEarly ? &umax : nullptr);
+  float eU = 0.f, eisc = 1.f, eus = 1.f, eius = 1.f;  // kEarly: bound and scales of the current layer input
+  halfx8 ecs[2];  // kEarly: k-step-0 split of the current layer input's tile 0
+  if constexpr (kEarly) {
+    const X3Halves uq = x3_halves(umax);
+    umax = fmaxf(uq.lo, uq.hi);
+    eU = __builtin_fmaf(op.x3_rb[0][0], umax, op.x3_rb[0][1]);
+    x3_scale_from(eU, nh > 1 ? opc.kw1 : kw_last, eisc, eus, eius);
+    x3_act_tile<NT, false>(hb[0], eisc, act);
+    split8h<0>(hb[0], ecs[0], ecs[1]);
+  }
+  // Hidden layers 1..n_hidden-1 (:343-345), T groups each.  bf16x3: the
+  // biases seed the accumulators.  f16x2: they seed them divided by the
+  // unscale (exact: powers of two) and the accumulators are multiplied
+  // by it afterwards (kSeedScaled).
+#ifndef ZF_X3_SEEDSCALED
+#define ZF_X3_SEEDSCALED 0
+#endif
+  // f16x2 at hidden 128 (the slot schedule): zero-seeded accumulators and
+  // one fma per value at the layer end (acc * us + bias) instead of a
+  // bias * ius seed and an acc * us unscale (two multiplies per value)
+  // (OACT too since round 5: a seeded bias sets the magnitude every MFMA
+  // accumulation rounds at; sigmoid / softplus fold C colsum(W) into it,
+  // 1e3-1e4 in the tiny-activation regime, where the zero-seeded sums of
+  // the small centred terms plus one finish fma round far less)
+  constexpr bool kSeedScaled = NT == 2 && (ZF_X3_SEEDSCALED || !kPipe);
+  // the hidden layers of a dim-pair flow (d8, d16: PAIRS, 2 waves per
+  // SIMD) and of hidden-256 flows (cfg5: T = 8, one wave per SIMD) take
+  // the f16x2 slot schedule too: only the last layer, which re-reads its
+  // input once per pair, keeps the plain group steps (d8 -2.1%, cfg5
+  // -3.4% kernel time)
+#ifndef ZF_X3_WIDE_PIPE
+#define ZF_X3_WIDE_PIPE 1
+#endif
+#ifndef ZF_X3_PAIRS_PIPE
+#define ZF_X3_PAIRS_PIPE 1
+#endif
+  constexpr bool kPipeH = kPipe || (ZF_X3_PAIRS_PIPE && (T == 4 || ZF_X3_WIDE_PIPE) && NT == 2 && !OACT);
+  // OACT with a narrowed activation set: the layer input's tiles 1..T-1
+  // activated inside the group steps (x3_step_pipe AS), like the swish
+#ifndef ZF_X3_ACTIN
+#define ZF_X3_ACTIN 1
+#endif
+  // (the centred set only: the five-way plain set spills 40 VGPRs that way, -13% on relu)
+  constexpr bool kActIn = ZF_X3_ACTIN && NT == 2 && ASET == 2 && kPipeH;
+  constexpr bool kSeedScaledH = NT == 2 && (ZF_X3_SEEDSCALED || !kPipeH);
+  // Three waves share a SIMD at hidden 128: the one streaming weight
+  // groups (MFMAs) wins issue arbitration over one in its VALU-only
+  // phases (layer 0, spline), so the matrix pipe idles less (+1.5% cfg2,
+  // +1.2% d8; nothing to arbitrate at hidden 256, one wave per SIMD).
+#if ZF_X3_ABL != 4  // tuning ablation 4: no issue priority
+  if constexpr (T == 4) __builtin_amdgcn_s_setprio(2);
+#endif
+  X3T(1);
+  if constexpr (kEarly) {
+    float eM = eU;  // max |v'| of the current layer input's pre-activations (exact from layer 2 on)
+    for (int l = 1; l < nh; ++l) {
+      // the next layer's input bound and scales (its tile 0 is swished in this layer's last
+      // step), from the exact maximum of this layer's input, so bounds never compound
+      const float nU = __builtin_fmaf(op.x3_rb[l][0], eM, op.x3_rb[l][1]);
+      float nisc, nus, nius;
+      x3_scale_from(nU, l + 1 < nh ? op.x3_kw[l + 1] : kw_last, nisc, nus, nius);
+      floatx16 acc[T];
+#pragma unroll
+      for (int o = 0; o < T; ++o) acc[o] = floatx16{0};
+      float mx;
+      x3_layer_early<T, T, true, 0, 0, RES>(x3, pipe, hb, acc, lane, par + b_rel + (l - 1) * (T * 32), hh, ecs, eisc, eus,
+                                 nisc, mx);
+#pragma unroll
+      for (int o = 0; o < T; ++o) hb[o] = acc[o];
+      eU = nU; eisc = nisc; eus = nus; eius = nius;
+      const X3Halves mq = x3_halves(mx);
+      eM = fmaxf(mq.lo, mq.hi);
+    }
+  } else
+  for (int l = 1; l < nh; ++l) {
+    floatx16 acc[T];
+    float isc = 1.f, us = 1.f, ius = 1.f;
+    if constexpr (NT == 2) {
+      x3_act_scale<T, OACT>(hb, l == 1 ? opc.kw1 : op.x3_kw[l], isc, us, ius, act);
+      // OACT: every tile here, outside the MFMA stream (the switch there
+      // would cost a third of the waves)
+#pragma unroll
+      for (int o = 0; o < (OACT && !kActIn ? T : 1); ++o) x3_act_tile<NT, OACT, ASET>(hb[o], isc, act);
+    }
+    const float* bl_l = par + b_rel + (l - 1) * (T * 32);
+#pragma unroll
+    for (int o = 0; o < T; ++o)
+      acc[o] = NT == 3 ? bias_acc(bl_l + o * 32, hh)
+                       : (kSeedScaledH ? bias_acc(bl_l + o * 32, hh) * ius : floatx16{0});
+    const float* bh = (NT == 2 && !kSeedScaledH) ? bl_l : nullptr;
+    if constexpr (kPipeH) {
+      typename XT<NT>::E cs[NT];
+      splitk<NT, 0>(hb[0], cs);
+      halfx8 fs1[2];  // ZF_X3_FUSED: the k-step 1 terms carried between group steps
+      x3_layer_pipe<NT, T, T, NT == 2 && !kSeedScaledH, OACT, 0, kActIn ? ASET : 0>(x3, pipe, hb, acc, lane, bh, hh,
+                                                                                 cs, isc, us,
+                                                             act, fs1);
+    } else {
+      x3_layer<NT, T, T, true, OACT>(x3, pipe, hb, acc, lane, bh, hh, isc, us, act);
+    }
+    if constexpr (kSeedScaledH) {
+#pragma unroll
+      for (int o = 0; o < T; ++o) acc[o] *= us;
+    }
+    const int nsw = NT == 2 ? 0 : (!OACT && (l + 1 < nh || kLastSW)) ? 1 : T;
+#pragma unroll
+    for (int o = 0; o < T; ++o) {
+      if (o < nsw) {
+        if constexpr (OACT) {
+          hb[o] = acc[o];
+          x3_act_tile<3, true>(hb[o], 1.f, act);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) hb[o][r] = swish(acc[o][r]);
+        }
+      } else {
+        hb[o] = acc[o];
+      }
+    }
+  }
+  X3T(2);
+  // Last Dense (:346-347), one pair of transformed dims at a time: lane
+  // half h, tile o, register r = parameter 16*o + r of dim 2*pair + h.
+  float ldn = 0.f;  // this coupling's log-det, summed in dim order (utils.py:139)
+  // PAIRS == false: one pair (dt <= 2), and the hidden activations are
+  // dead once the last layer has consumed them.
+  const int npair = PAIRS ? (dt + 1) / 2 : 1;
+  float lisc = 1.f, lus = 1.f, lius = 1.f;  // f16x2 scales of the last layer's input (all pairs)
+  if constexpr (kEarly) {
+    lisc = eisc; lus = eus; lius = eius;  // tile 0 swished, ecs its split
+  } else if constexpr (NT == 2) {
+    x3_act_scale<T, OACT>(hb, kw_last, lisc, lus, lius, act);
+    // PAIRS: the input is read once per dim pair, so swish it whole here
+#pragma unroll
+    for (int o = 0; o < T; ++o)
+      if (o == 0 || !kLastSW || (OACT && !(kActIn && kPipe))) x3_act_tile<NT, OACT, ASET>(hb[o], lisc, act);
+  }
+#ifndef ZF_X3_PRESPLIT
+#define ZF_X3_PRESPLIT 1
+#endif
+  // PAIRS at hidden 128 (f16x2): the last layer's input split once for
+  // all pairs (d8 -1.0%; at hidden 256, one wave per SIMD, the per-pair
+  // re-split hides in the MFMA gaps and the pre-split cost 5.6%)
+  constexpr bool kPre = ZF_X3_PRESPLIT && PAIRS && T == 4 && NT == 2 && !OACT;
+  halfx8 sp[kPre ? T : 1][2][2];
+  if constexpr (kPre) {
+#pragma unroll
+    for (int q = 0; q < T; ++q) {
+      split8h<0>(hb[q], sp[q][0][0], sp[q][0][1]);
+      split8h<1>(hb[q], sp[q][1][0], sp[q][1][1]);
+    }
+  }
+  for (int pr = 0; pr < npair; ++pr) {
+    // The bias seeds the accumulators when the hidden activations stay
+    // live across pairs anyway; otherwise it joins in the last step, when
+    // the first input tiles are dead (fewer registers at the peak);
+    // f16x2 always joins it at the end, with the unscale.
+    const float* bl = par + blast_rel + pr * TL * 32;
+    floatx16 pa[TL];
+    constexpr bool kSeed = PAIRS && NT == 3;
+#pragma unroll
+    for (int o = 0; o < TL; ++o)
+      pa[o] = kSeed ? bias_acc(bl + o * 32, hh) : (kSeedScaled ? bias_acc(bl + o * 32, hh) * lius : floatx16{0});
+    X3T(3);
+    if constexpr (kEarly) {
+      float mx;
+      x3_layer_early<T, TL, false, kPreSP, 0, RES>(x3, pipe, hb, pa, lane, bl, hh, ecs, lisc, lus, 0.f, mx);
+    } else if constexpr (kPre) {
+      x3_layer_pre<T, TL>(x3, pipe, sp, pa, lane);
+    } else if constexpr (kPipe) {
+      typename XT<NT>::E cs[NT];
+      splitk<NT, 0>(hb[0], cs);
+      halfx8 fs1[2];
+      x3_layer_pipe<NT, T, TL, !kSeedScaled, OACT, 0, kActIn ? ASET : 0>(x3, pipe, hb, pa, lane, bl, hh, cs, lisc,
+                                                                         lus, act, fs1);
+    } else {
+      x3_layer<NT, T, TL, kLastSW, OACT>(x3, pipe, hb, pa, lane, (kSeed || kSeedScaled) ? nullptr : bl, hh,
+                                         lisc, lus, act);
+    }
+    if constexpr (kSeedScaled) {
+#pragma unroll
+      for (int o = 0; o < TL; ++o) pa[o] *= lus;
+    }
+    if constexpr (T == 4) __builtin_amdgcn_s_setprio(0);
+    X3T(4);
+    // ONE at K = 16: tile 0 holds the widths on lane half 0 and the
+    // heights on half 1, so each half normalises its own 16 (squareplus,
+    // sum in order, quotients: the same operations per value) and one
+    // exchange per knot gives both halves both; tile 1's slopes (half 0)
+    // go to both halves.  Other ONE shapes exchange the whole row first.
+    constexpr bool kSplitWH = ONE && K == 16;
+    float P[NPV];
+#pragma unroll
+    for (int o = 0; o < TL; ++o)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if constexpr (kSplitWH) {
+          if (o == 0) P[r] = pa[0][r];
+          else  // slope r of half 0, on both halves
+            P[2 * K + r] = x3_halves(pa[1][r]).lo;
+        } else if constexpr (ONE) {  // both halves end up with all of the dim's parameters
+          const X3Halves q = x3_halves(pa[o][r]);
+          P[32 * o + r] = q.lo;
+          P[32 * o + 16 + r] = q.hi;
+        } else {
+          P[16 * o + r] = pa[o][r];
+        }
+      }
+    X3M(11);
+#if ZF_X3_ABL == 10 || ZF_X3_ABL == 11  // tuning: 64 extra VALU (10: v_add, 11: v_exp) in the spline phase
+#pragma unroll
+    for (int q2 = 0; q2 < 64; ++q2) {
+      float dd;
+      if (ZF_X3_ABL == 10) asm volatile("v_add_f32 %0, %1, %2" : "=v"(dd) : "v"(pa[0][q2 & 15]), "v"(pa[1][q2 & 15]));
+      else asm volatile("v_exp_f32 %0, %1" : "=v"(dd) : "v"(pa[0][q2 & 15]));
+    }
+#endif
+    // normalize_spline_params (utils.py:37-62) + RQ spline (utils.py:65-250)
+    const int d = 2 * pr + hh;
+    const bool dact = d < dt;  // the upper half idles on an odd last dim
+    float ldv = 0.f;
+    {
+      float* xp = xs + wrap((dact ? d : 0) + rot, D) * 32 + s;
+      const float xv = *xp;
+#ifndef ZF_X3_BSEARCH
+#define ZF_X3_BSEARCH 0
+#endif
+      RqsBin bin;
+      bool binned = false;
+      if constexpr (ZF_X3_BSEARCH && !kSplitWH && !kPreSP && (K == 8 || K == 16 || K == 32 || K == 64)) {
+        if (klit) {  // the halving search takes unpadded knots only, not yet squareplus'd ones
+          bin = x3_bin<!INV, K, OACT, true>(xv, P, kc);
+          binned = true;
+        }
+      }
+      if (!binned) {
+        float w[K], hg[K];
+        const float bc = kc.c * kc.rnorm;
+        if constexpr (kSplitWH) {
+          float sw = 0.f;  // half 0: the widths' sum, half 1: the heights'
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            w[j] = kPreSP ? P[j] : x3_squareplus2_t<OACT>(P[j]);
+            sw = sw + w[j];
+          }
+          const float a = rcp_refined(sw) * kc.rnorm;
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            const X3Halves q = x3_halves(__builtin_fmaf(w[j], a, bc));
+            w[j] = q.lo;
+            hg[j] = q.hi;
+          }
+        } else {
+          float sx = 0.f, sy = 0.f;
+#pragma unroll
+          for (int j = 0; j < K; ++j) {  // squareplus + sums in order (utils.py:30-33)
+            w[j] = kPreSP ? P[j] : x3_squareplus2_t<OACT>(P[j]);
+            hg[j] = kPreSP ? P[K + j] : x3_squareplus2_t<OACT>(P[K + j]);
+            sx = sx + w[j];
+            sy = sy + hg[j];
+          }
+          // (v / sum + c) / (1 + c K) as one fma per knot (v and sum both
+          // 2*squareplus: the same quotient bits): the parameters
+          // themselves already differ from the reference's in the last ulp
+          // (GEMM summation order), so correctly rounded divisions buy nothing.
+          const float ax = rcp_refined(sx) * kc.rnorm, ay = rcp_refined(sy) * kc.rnorm;
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            w[j] = __builtin_fmaf(w[j], ax, bc);
+            hg[j] = __builtin_fmaf(hg[j], ay, bc);
+          }
+        }
+        X3M(12);
+        float sl[K - 1];  // raw slope logits; the bin's two get squareplus'd
+#pragma unroll
+        for (int j = 0; j < K - 1; ++j) sl[j] = P[2 * K + j];
+#ifndef ZF_X3_EXECBIN
+#define ZF_X3_EXECBIN 1
+#endif
+        // the latch as exec-masked moves (rqs_bin_exec): -15% of the spline phase's VALU issue
+        const auto spf = [](float v) { return v == 0.f ? 1.f : x3_squareplus_t<OACT>(v); };
+        if constexpr (ZF_X3_EXECBIN && K % 8 == 0) bin = rqs_bin_exec<!INV, K>(xv, w, hg, sl, spf, padlast);
+        else bin = rqs_bin_monotone<!INV, K>(xv, w, hg, sl, spf, padlast);
+        X3M(13);
+      }
+      float yv;
+      if (!INV) {
+        float l;
+        x3_forward_eval(xv, bin, yv, l);
+        ldv = dact ? l : 0.f;
+      } else {
+        yv = rqs_inverse_eval(xv, bin);
+      }
+      if (dact) *xp = yv;
+    }
+    wave_lds_sync();
+    if (!INV) {
+      const X3Halves q = x3_halves(ldv);
+      ldn = ldn + q.lo;
+      if (2 * pr + 1 < dt) ldn = ldn + q.hi;
+    }
+  }
+  if (!INV) ld = ld + ldn;  // Chain: log_det += ld (bijectors.py:110)
+  X3T(5);
+}
+
+// Resident form (f16x2, hidden 128, one streamed hidden layer, one dim pair):
+// one block of 12 waves per CU keeps a whole coupling's packed weights in LDS
+// and runs coupling-major — load coupling c's span once, run it over all of
+// the block's rows, then load coupling c + 1 — so no weight byte is streamed
+// per 128-row block, the group steps have no DMA wait and no block barrier
+// (x3_step_slots RES), and the waves of a CU are independent of each other
+// between two coupling barriers.  A tile's state (x and the running log-det)
+// crosses a coupling boundary through a device scratch, [tile][D + 1][32]
+// floats updated in place: a tile belongs to one wave per pass, passes are
+// separated by the block barrier, and blocks own disjoint rows.  The next
+// tile's state is DMA'd into the wave's second state buffer while the
+// current tile computes.  Per-row arithmetic is x3_nsc's, instruction for
+// instruction, and the NLL partials are formed in flow_epilogue's order, so
+// every output has the streaming form's bits.
+constexpr int kX3ResWaves = 12;  // three waves per SIMD, as the streaming form's three blocks per CU
+
+// LDS: resident span | one small-parameter region | [12][2][DS + 1][32] state | one fp64 sum per tile
+inline size_t x3_res_lds_bytes(size_t span, int par_bytes, int DS, long long tiles_per_block) {
+  return span + (size_t)par_bytes + (size_t)kX3ResWaves * 2 * (DS + 1) * 32 * 4 + (size_t)tiles_per_block * 8;
+}
+
+// DMA one tile's state (scratch: x [D][32], then the log-det [32]) into a
+// state buffer ([DS][32] x | c, then the log-det [32]); no VGPR is held.
+__device__ __forceinline__ void x3r_fetch(const float* __restrict__ st, float* buf, int D, int DS, int lane) {
+#pragma nounroll
+  for (int j = 0; j < D; j += 2)
+    if (j + (lane >> 5) < D)
+      __builtin_amdgcn_global_load_lds((const void*)(st + j * 32 + lane),
+                                       (__attribute__((address_space(3))) void*)(buf + j * 32), 4, 0, 0);
+  if (lane < 32)
+    __builtin_amdgcn_global_load_lds((const void*)(st + D * 32 + lane),
+                                     (__attribute__((address_space(3))) void*)(buf + DS * 32), 4, 0, 0);
+}
+
+template <int K, bool ONE, bool INV>
+__global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
+    const DevFlow* __restrict__ F, const float* __restrict__ blob, const char* __restrict__ x3,
+    const float* __restrict__ xin, const float* __restrict__ cin, float* __restrict__ y_out,
+    const float* __restrict__ ld_in, float* __restrict__ ld_out, float* __restrict__ lp_out,
+    double* __restrict__ block_partial, int op_begin, int op_end, long long N, unsigned long long seed, int gen,
+    float* __restrict__ state, int slots_per_block, int span_bytes) {
+  constexpr int NT = 2, T = 4, NW = kX3ResWaves;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int D = F->D;
+  const int C = F->C;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int s = lane & 31;
+  const int hh = lane >> 5;
+  const int PB = F->x3_par_bytes;
+  const int DS = D + C;
+  const int SB = (DS + 1) * 32;  // floats of one state buffer
+  const int ST = (D + 1) * 32;   // floats of one tile in the scratch
+  char* par_lds = lds + span_bytes;
+  float* xs0 = reinterpret_cast<float*>(par_lds + PB) + wave * (2 * SB);
+  double* s_part = reinterpret_cast<double*>(reinterpret_cast<float*>(par_lds + PB) + NW * 2 * SB);
+  // this block's rows: slots_per_block whole 128-row NLL slots; nt = its tiles that hold a row
+  const long long slot0 = (long long)blockIdx.x * slots_per_block;
+  const long long tile0 = slot0 * 4;
+  const long long left = (N + kTile - 1) / kTile - tile0;
+  const int nt = left <= 0 ? 0 : (left < 4ll * slots_per_block ? (int)left : 4 * slots_per_block);
+  for (int i = threadIdx.x; i < 4 * slots_per_block; i += NW * 64) s_part[i] = 0.0;  // ordered by the first pass's barrier
+
+  X3Pipe pipe;
+  pipe.nxt = nullptr;
+  pipe.wave = wave;
+  pipe.par_src = nullptr;
+  pipe.par_dst = nullptr;
+  pipe.par_pieces = 0;
+  X3Tr tr = {};
+  const int nq = op_end - op_begin;
+  int rot0 = 0;  // the roll rotation at the start of the pass (the same for every row)
+  bool first = true;
+  for (int q = 0; q < nq;) {
+    // this pass: the ops up to and including the next NSC; the last pass takes the ops behind it too
+    int nsc = -1, seg_end = nq;
+    for (int r = q; r < nq; ++r)
+      if (F->ops[INV ? (op_end - 1 - r) : (op_begin + r)].kind == ZF_OP_NSC) {
+        if (nsc < 0) {
+          nsc = r;
+        } else {
+          seg_end = nsc + 1;
+          break;
+        }
+      }
+    const bool last = seg_end == nq;
+    // every wave of every block passes these two barriers once per pass, whatever its tile list
+    __syncthreads();  // all waves are done with the previous coupling's weights
+    if (nsc >= 0 && nt > 0) {
+      const DevOp& fo = F->ops[INV ? (op_end - 1 - nsc) : (op_begin + nsc)];
+      const int pieces = (T * (fo.n_hidden - 1) * group_bytes<NT>(T) + T * group_bytes<NT>(fo.x3_tlast)) >> 10;
+      x3_dma(x3 + fo.x3, lds, pieces, wave, lane, NW);
+      x3_dma(reinterpret_cast<const char*>(blob + fo.bn), par_lds, fo.x3_par_pieces, wave, lane, NW);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // the span and the parameters are complete
+
+    int cur = 0;
+    if (!first && wave < nt) x3r_fetch(state + (tile0 + wave) * ST, xs0, D, DS, lane);
+    for (int t = wave; t < nt; t += NW) {
+      float* xs = xs0 + cur * SB;
+      const long long tile = tile0 + t;
+      // The tile's load and store code takes its lane index through an
+      // opaque copy, so its per-lane addresses are formed here and not kept
+      // in registers across the coupling as invariants of the tile loop.
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      {
+        const int s1 = ln & 31, h1 = ln >> 5;
+        const long long row1 = tile * kTile + s1;
+        const bool valid1 = row1 < N;
+        if (first) {
+          load_state(xs, xin, row1, valid1, D, s1, h1, F, seed, INV ? gen : 0);
+        } else if (t == wave) {
+          // later tiles' state was waited for before the previous tile's stores (below)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+#pragma nounroll
+        for (int j = h1; j < C; j += 2) xs[(D + j) * 32 + s1] = valid1 ? cin[row1 * C + j] : 0.f;
+      }
+      wave_lds_sync();
+      float ld;
+      if (first) {
+        const long long row1 = tile * kTile + (ln & 31);
+        ld = (ld_in != nullptr && row1 < N) ? ld_in[row1] : 0.f;
+      } else {
+        ld = xs[DS * 32 + (ln & 31)];
+        if (t + NW < nt) x3r_fetch(state + (tile + NW) * ST, xs0 + (cur ^ 1) * SB, D, DS, ln);
+      }
+      int rot = rot0;
+      for (int r = q; r < seg_end; ++r) {
+        const DevOp& op = F->ops[INV ? (op_end - 1 - r) : (op_begin + r)];
+        const X3Sc opc = x3_scalars<INV>(op);
+        if (opc.kind == ZF_OP_ROLL) {
+          rot = pmod(INV ? rot + opc.shift : rot - opc.shift, D);
+        } else if (opc.kind == ZF_OP_SHIFT_BOUNDS) {
+          shift_bounds_op<INV>(blob + opc.sb, xs, s, hh, rot, D, ld);
+        } else {
+          // an opaque zero keeps the span's and the parameters' per-lane LDS
+          // addresses inside the coupling (hoisted out of the tile loop as
+          // loop invariants they cost 44 spilled VGPRs)
+          int zoff = 0;
+          asm volatile("" : "+s"(zoff));
+          pipe.cur = lds + zoff;
+          pipe.g = 0;
+          x3_nsc<NT, K, T, false, ONE, INV, false, 0, true>(
+              op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, rot, D, s, hh, lane, ld, tr);
+        }
+      }
+      // the next tile's state has landed (issued a whole tile ago), so the
+      // next iteration does not wait behind this tile's own stores
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("" : "+v"(ln));
+      const int s2 = ln & 31, h2 = ln >> 5;
+      const long long row = tile * kTile + s2;
+      const bool valid = row < N;
+      if (!last) {
+        float* st = state + tile * ST;
+#pragma nounroll
+        for (int d = h2; d < D; d += 2) st[d * 32 + s2] = xs[d * 32 + s2];
+        if (h2 == 0) st[D * 32 + s2] = ld;
+      } else {
+        if (lp_out != nullptr) {
+          const double v = flow_lp_rows(F, xs, s2, h2, rot, D, row, valid, ld, lp_out, block_partial != nullptr);
+          if (block_partial != nullptr && ln == 0) s_part[t] = v;
+        }
+        flow_out_rows(xs, s2, h2, rot, D, row, valid, ld, y_out, ld_out);
+      }
+      wave_lds_sync();
+      cur ^= 1;
+    }
+    for (int r = q; r < seg_end; ++r) {
+      const DevOp& op = F->ops[INV ? (op_end - 1 - r) : (op_begin + r)];
+      if (op.kind == ZF_OP_ROLL) rot0 = pmod(INV ? rot0 + op.shift : rot0 - op.shift, D);
+    }
+    q = seg_end;
+    first = false;
+  }
+  // NLL partials: slot sums in tile order, as flow_epilogue's thread-0 loop
+  __syncthreads();
+  if (lp_out != nullptr && block_partial != nullptr) {
+    const int ns = (nt + 3) / 4;
+    for (int i = threadIdx.x; i < ns; i += NW * 64) {
+      double acc = 0.0;
+      for (int w = 0; w < 4; ++w) acc += s_part[4 * i + w];
+      block_partial[slot0 + i] = acc;
+    }
+  }
+}
+
+template <int K, bool ONE>
+int launch_x3r(const X3Launch& a, bool inverse) {
+  const size_t lds = x3_res_lds_bytes((size_t)a.res_span, a.par_bytes, a.D + a.C, 4ll * a.res_slots);
+  if (lds > 160 * 1024 || a.res_state == nullptr) return enotsup("resident split-MFMA kernel: shape");
+  if (inverse)
+    hipLaunchKernelGGL((flow_kernel_x3r<K, ONE, true>), dim3((unsigned)a.res_blocks), dim3(kX3ResWaves * 64), lds,
+                       a.stream, a.desc, a.blob, (const char*)a.x3, a.x, a.c, a.y, a.ld_in, a.ld_out, a.lp, a.part,
+                       a.op_begin, a.op_end, a.N, a.seed, a.gen, a.res_state, a.res_slots, a.res_span);
+  else
+    hipLaunchKernelGGL((flow_kernel_x3r<K, ONE, false>), dim3((unsigned)a.res_blocks), dim3(kX3ResWaves * 64), lds,
+                       a.stream, a.desc, a.blob, (const char*)a.x3, a.x, a.c, a.y, a.ld_in, a.ld_out, a.lp, a.part,
+                       a.op_begin, a.op_end, a.N, a.seed, a.gen, a.res_state, a.res_slots, a.res_span);
+  ZF_CHECK_LAUNCH("flow_kernel_x3r");
+  return ZF_OK;
+}
+
 template <int NT, int K, int T, bool PAIRS, bool ONE, bool INV, bool OACT, int ASET = 0>
 __global__ __launch_bounds__(kX3Waves * 64, (x3_occupancy<T, K, PAIRS>())) void flow_kernel_x3(
     const DevFlow* __restrict__ F, const float* __restrict__ blob, const char* __restrict__ x3,
@@ -1461,7 +2074,6 @@ __global__ __launch_bounds__(kX3Waves * 64, (x3_occupancy<T, K, PAIRS>())) void 
     unsigned long long seed, int gen) {
   // last-layer tiles per dim pair: 16 parameters per lane half (ONE: 32 of one dim per tile)
   constexpr int TL = ONE ? (3 * K - 1 + 31) / 32 : (3 * K - 1 + 15) / 16;
-  constexpr int NPV = ONE ? 32 * TL : 16 * TL;  // spline parameters held per lane
   constexpr int NW = kX3Waves;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int D = F->D;
@@ -1509,32 +2121,14 @@ __global__ __launch_bounds__(kX3Waves * 64, (x3_occupancy<T, K, PAIRS>())) void 
   float ld = (ld_in != nullptr && valid) ? ld_in[row] : 0.f;
   int rot = 0;
   wave_lds_sync();
+  X3Tr tr;
 #ifdef ZF_X3_TRACE
-  // slots: 0 start->first NSC, 1 layer 0, 2 hidden layers, 3 hidden->last
-  // transition, 4 last layer, 5 spline, 6 epilogue, 7 barrier waits (inside
-  // 2 and 4), 8 total, 9 couplings, 10 other ops
-  unsigned long long tacc[kX3TraceSlots] = {};
+  for (int k = 0; k < kX3TraceSlots; ++k) tr.tacc[k] = 0;
   pipe.tbar = 0;
   pipe.tdma = 0;
   pipe.tgrp = 0;
   const unsigned long long t_begin = X3T_NOW();
-  unsigned long long t_last = t_begin;
-#define X3T(k)                                   \
-  {                                              \
-    const unsigned long long t_ = X3T_NOW();     \
-    tacc[k] += t_ - t_last;                      \
-    t_last = t_;                                 \
-  }
-#elif defined(ZF_X3_MARK)
-  // tuning only: phase markers in the .s for per-phase static instruction counts
-#define X3T(k) asm volatile(";ZFMARK " #k)
-#else
-#define X3T(k)
-#endif
-#ifdef ZF_X3_MARK
-#define X3M(k) asm volatile(";ZFMARK " #k)
-#else
-#define X3M(k)
+  tr.t_last = t_begin;
 #endif
   pipe.par_src = nullptr;
   pipe.par_dst = nullptr;
@@ -1559,7 +2153,7 @@ __global__ __launch_bounds__(kX3Waves * 64, (x3_occupancy<T, K, PAIRS>())) void 
     } else {  // ZF_OP_NSC, bijectors.py:329-371
       X3T(0);
 #ifdef ZF_X3_TRACE
-      tacc[9] += 1;
+      tr.tacc[9] += 1;
 #endif
       {  // the next NSC's stream and parameters from this op's own record
         const bool has_next = opc.nxt >= op_begin && opc.nxt < op_end;
@@ -1571,349 +2165,8 @@ __global__ __launch_bounds__(kX3Waves * 64, (x3_occupancy<T, K, PAIRS>())) void 
       pipe.g = 0;
       const float* par = reinterpret_cast<const float*>(par_lds + (nsc_i & 1) * PB);
       ++nsc_i;
-      const int nh = opc.nh, act = opc.act, dt = opc.dt, kw_last = opc.kw_last;
-      // this coupling's knots: a chain may mix knot counts up to the kernel's K
-      // (x3_padded_knots); K - 1 real knots put the idx == K sliver at the
-      // padded knot (rqs_bin_monotone padlast)
-      const KnotConsts kc(opc.kreal);
-      const bool padlast = opc.kreal == K - 1;
-#ifdef ZF_X3_MARK
-      const bool klit = true;  // marker builds: count one x3_bin copy
-#else
-      const bool klit = opc.kreal == K;  // x3_bin: the knot constants as literals
-#endif
-      // hidden biases are consecutive T x 32 blocks after Dense_0's (zf_flow.hip: b[l] = b[0] + l T 32)
-      const long long b_rel = opc.b_rel + T * 32, blast_rel = opc.blast_rel;
-      floatx16 hb[T];
-      // The swish of a layer's output is deferred tile by tile into the next
-      // streamed layer (x3_step, SW) — except before a PAIRS last layer,
-      // which passes over its input once per dim pair.
-      constexpr bool kLastSW = !PAIRS;
-      constexpr bool kPipe = T == 4 && !PAIRS;
-      // f16x2: every layer leaves raw pre-activations; the next streamed
-      // layer scales and swishes them (act_swish) as it goes.
-      // bf16x3 OACT: every tile's activation at the layer end (no switch inside
-      // the group steps)
-#ifndef ZF_X3_EARLY
-#define ZF_X3_EARLY 1
-#endif
-      // f16x2 swish at hidden 128 (one dim pair): scales from bounds (x3_early_scale)
-      constexpr bool kEarly = ZF_X3_EARLY && NT == 2 && !OACT && kPipe;
-      // kEarly: the last layer's width / height tiles leave its last group
-      // step as 2 squareplus (x3_step_slots_last SPT): K / 8 tiles of 16 per
-      // lane half (one dim per half); ONE at K = 16: tile 0 (widths on half 0,
-      // heights on half 1, the kSplitWH layout)
-#ifndef ZF_X3_PRESP
-#define ZF_X3_PRESP 1
-#endif
-      constexpr int kPreSP = (!ZF_X3_PRESP || !kEarly) ? 0 : !ONE ? K / 8 : (K == 16 ? 1 : 0);
-      float umax = 0.f;
-      x3_layer0<T, OACT>(opc, par, xs, rot, D, s, hh, lane, hb, NT == 2 ? 0 : (!OACT && (nh > 1 || kLastSW)) ? 1 : T,
-                         kEarly ? &umax : nullptr);
-      float eU = 0.f, eisc = 1.f, eus = 1.f, eius = 1.f;  // kEarly: bound and scales of the current layer input
-      halfx8 ecs[2];  // kEarly: k-step-0 split of the current layer input's tile 0
-      if constexpr (kEarly) {
-        const X3Halves uq = x3_halves(umax);
-        umax = fmaxf(uq.lo, uq.hi);
-        eU = __builtin_fmaf(op.x3_rb[0][0], umax, op.x3_rb[0][1]);
-        x3_scale_from(eU, nh > 1 ? opc.kw1 : kw_last, eisc, eus, eius);
-        x3_act_tile<NT, false>(hb[0], eisc, act);
-        split8h<0>(hb[0], ecs[0], ecs[1]);
-      }
-      // Hidden layers 1..n_hidden-1 (:343-345), T groups each.  bf16x3: the
-      // biases seed the accumulators.  f16x2: they seed them divided by the
-      // unscale (exact: powers of two) and the accumulators are multiplied
-      // by it afterwards (kSeedScaled).
-#ifndef ZF_X3_SEEDSCALED
-#define ZF_X3_SEEDSCALED 0
-#endif
-      // f16x2 at hidden 128 (the slot schedule): zero-seeded accumulators and
-      // one fma per value at the layer end (acc * us + bias) instead of a
-      // bias * ius seed and an acc * us unscale (two multiplies per value)
-      // (OACT too since round 5: a seeded bias sets the magnitude every MFMA
-      // accumulation rounds at; sigmoid / softplus fold C colsum(W) into it,
-      // 1e3-1e4 in the tiny-activation regime, where the zero-seeded sums of
-      // the small centred terms plus one finish fma round far less)
-      constexpr bool kSeedScaled = NT == 2 && (ZF_X3_SEEDSCALED || !kPipe);
-      // the hidden layers of a dim-pair flow (d8, d16: PAIRS, 2 waves per
-      // SIMD) and of hidden-256 flows (cfg5: T = 8, one wave per SIMD) take
-      // the f16x2 slot schedule too: only the last layer, which re-reads its
-      // input once per pair, keeps the plain group steps (d8 -2.1%, cfg5
-      // -3.4% kernel time)
-#ifndef ZF_X3_WIDE_PIPE
-#define ZF_X3_WIDE_PIPE 1
-#endif
-#ifndef ZF_X3_PAIRS_PIPE
-#define ZF_X3_PAIRS_PIPE 1
-#endif
-      constexpr bool kPipeH = kPipe || (ZF_X3_PAIRS_PIPE && (T == 4 || ZF_X3_WIDE_PIPE) && NT == 2 && !OACT);
-      // OACT with a narrowed activation set: the layer input's tiles 1..T-1
-      // activated inside the group steps (x3_step_pipe AS), like the swish
-#ifndef ZF_X3_ACTIN
-#define ZF_X3_ACTIN 1
-#endif
-      // (the centred set only: the five-way plain set spills 40 VGPRs that way, -13% on relu)
-      constexpr bool kActIn = ZF_X3_ACTIN && NT == 2 && ASET == 2 && kPipeH;
-      constexpr bool kSeedScaledH = NT == 2 && (ZF_X3_SEEDSCALED || !kPipeH);
-      // Three waves share a SIMD at hidden 128: the one streaming weight
-      // groups (MFMAs) wins issue arbitration over one in its VALU-only
-      // phases (layer 0, spline), so the matrix pipe idles less (+1.5% cfg2,
-      // +1.2% d8; nothing to arbitrate at hidden 256, one wave per SIMD).
-#if ZF_X3_ABL != 4  // tuning ablation 4: no issue priority
-      if constexpr (T == 4) __builtin_amdgcn_s_setprio(2);
-#endif
-      X3T(1);
-      if constexpr (kEarly) {
-        float eM = eU;  // max |v'| of the current layer input's pre-activations (exact from layer 2 on)
-        for (int l = 1; l < nh; ++l) {
-          // the next layer's input bound and scales (its tile 0 is swished in this layer's last
-          // step), from the exact maximum of this layer's input, so bounds never compound
-          const float nU = __builtin_fmaf(op.x3_rb[l][0], eM, op.x3_rb[l][1]);
-          float nisc, nus, nius;
-          x3_scale_from(nU, l + 1 < nh ? op.x3_kw[l + 1] : kw_last, nisc, nus, nius);
-          floatx16 acc[T];
-#pragma unroll
-          for (int o = 0; o < T; ++o) acc[o] = floatx16{0};
-          float mx;
-          x3_layer_early<T, T, true>(x3, pipe, hb, acc, lane, par + b_rel + (l - 1) * (T * 32), hh, ecs, eisc, eus,
-                                     nisc, mx);
-#pragma unroll
-          for (int o = 0; o < T; ++o) hb[o] = acc[o];
-          eU = nU; eisc = nisc; eus = nus; eius = nius;
-          const X3Halves mq = x3_halves(mx);
-          eM = fmaxf(mq.lo, mq.hi);
-        }
-      } else
-      for (int l = 1; l < nh; ++l) {
-        floatx16 acc[T];
-        float isc = 1.f, us = 1.f, ius = 1.f;
-        if constexpr (NT == 2) {
-          x3_act_scale<T, OACT>(hb, l == 1 ? opc.kw1 : op.x3_kw[l], isc, us, ius, act);
-          // OACT: every tile here, outside the MFMA stream (the switch there
-          // would cost a third of the waves)
-#pragma unroll
-          for (int o = 0; o < (OACT && !kActIn ? T : 1); ++o) x3_act_tile<NT, OACT, ASET>(hb[o], isc, act);
-        }
-        const float* bl_l = par + b_rel + (l - 1) * (T * 32);
-#pragma unroll
-        for (int o = 0; o < T; ++o)
-          acc[o] = NT == 3 ? bias_acc(bl_l + o * 32, hh)
-                           : (kSeedScaledH ? bias_acc(bl_l + o * 32, hh) * ius : floatx16{0});
-        const float* bh = (NT == 2 && !kSeedScaledH) ? bl_l : nullptr;
-        if constexpr (kPipeH) {
-          typename XT<NT>::E cs[NT];
-          splitk<NT, 0>(hb[0], cs);
-          halfx8 fs1[2];  // ZF_X3_FUSED: the k-step 1 terms carried between group steps
-          x3_layer_pipe<NT, T, T, NT == 2 && !kSeedScaledH, OACT, 0, kActIn ? ASET : 0>(x3, pipe, hb, acc, lane, bh, hh,
-                                                                                     cs, isc, us,
-                                                                 act, fs1);
-        } else {
-          x3_layer<NT, T, T, true, OACT>(x3, pipe, hb, acc, lane, bh, hh, isc, us, act);
-        }
-        if constexpr (kSeedScaledH) {
-#pragma unroll
-          for (int o = 0; o < T; ++o) acc[o] *= us;
-        }
-        const int nsw = NT == 2 ? 0 : (!OACT && (l + 1 < nh || kLastSW)) ? 1 : T;
-#pragma unroll
-        for (int o = 0; o < T; ++o) {
-          if (o < nsw) {
-            if constexpr (OACT) {
-              hb[o] = acc[o];
-              x3_act_tile<3, true>(hb[o], 1.f, act);
-            } else {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) hb[o][r] = swish(acc[o][r]);
-            }
-          } else {
-            hb[o] = acc[o];
-          }
-        }
-      }
-      X3T(2);
-      // Last Dense (:346-347), one pair of transformed dims at a time: lane
-      // half h, tile o, register r = parameter 16*o + r of dim 2*pair + h.
-      float ldn = 0.f;  // this coupling's log-det, summed in dim order (utils.py:139)
-      // PAIRS == false: one pair (dt <= 2), and the hidden activations are
-      // dead once the last layer has consumed them.
-      const int npair = PAIRS ? (dt + 1) / 2 : 1;
-      float lisc = 1.f, lus = 1.f, lius = 1.f;  // f16x2 scales of the last layer's input (all pairs)
-      if constexpr (kEarly) {
-        lisc = eisc; lus = eus; lius = eius;  // tile 0 swished, ecs its split
-      } else if constexpr (NT == 2) {
-        x3_act_scale<T, OACT>(hb, kw_last, lisc, lus, lius, act);
-        // PAIRS: the input is read once per dim pair, so swish it whole here
-#pragma unroll
-        for (int o = 0; o < T; ++o)
-          if (o == 0 || !kLastSW || (OACT && !(kActIn && kPipe))) x3_act_tile<NT, OACT, ASET>(hb[o], lisc, act);
-      }
-#ifndef ZF_X3_PRESPLIT
-#define ZF_X3_PRESPLIT 1
-#endif
-      // PAIRS at hidden 128 (f16x2): the last layer's input split once for
-      // all pairs (d8 -1.0%; at hidden 256, one wave per SIMD, the per-pair
-      // re-split hides in the MFMA gaps and the pre-split cost 5.6%)
-      constexpr bool kPre = ZF_X3_PRESPLIT && PAIRS && T == 4 && NT == 2 && !OACT;
-      halfx8 sp[kPre ? T : 1][2][2];
-      if constexpr (kPre) {
-#pragma unroll
-        for (int q = 0; q < T; ++q) {
-          split8h<0>(hb[q], sp[q][0][0], sp[q][0][1]);
-          split8h<1>(hb[q], sp[q][1][0], sp[q][1][1]);
-        }
-      }
-      for (int pr = 0; pr < npair; ++pr) {
-        // The bias seeds the accumulators when the hidden activations stay
-        // live across pairs anyway; otherwise it joins in the last step, when
-        // the first input tiles are dead (fewer registers at the peak);
-        // f16x2 always joins it at the end, with the unscale.
-        const float* bl = par + blast_rel + pr * TL * 32;
-        floatx16 pa[TL];
-        constexpr bool kSeed = PAIRS && NT == 3;
-#pragma unroll
-        for (int o = 0; o < TL; ++o)
-          pa[o] = kSeed ? bias_acc(bl + o * 32, hh) : (kSeedScaled ? bias_acc(bl + o * 32, hh) * lius : floatx16{0});
-        X3T(3);
-        if constexpr (kEarly) {
-          float mx;
-          x3_layer_early<T, TL, false, kPreSP>(x3, pipe, hb, pa, lane, bl, hh, ecs, lisc, lus, 0.f, mx);
-        } else if constexpr (kPre) {
-          x3_layer_pre<T, TL>(x3, pipe, sp, pa, lane);
-        } else if constexpr (kPipe) {
-          typename XT<NT>::E cs[NT];
-          splitk<NT, 0>(hb[0], cs);
-          halfx8 fs1[2];
-          x3_layer_pipe<NT, T, TL, !kSeedScaled, OACT, 0, kActIn ? ASET : 0>(x3, pipe, hb, pa, lane, bl, hh, cs, lisc,
-                                                                             lus, act, fs1);
-        } else {
-          x3_layer<NT, T, TL, kLastSW, OACT>(x3, pipe, hb, pa, lane, (kSeed || kSeedScaled) ? nullptr : bl, hh,
-                                             lisc, lus, act);
-        }
-        if constexpr (kSeedScaled) {
-#pragma unroll
-          for (int o = 0; o < TL; ++o) pa[o] *= lus;
-        }
-        if constexpr (T == 4) __builtin_amdgcn_s_setprio(0);
-        X3T(4);
-        // ONE at K = 16: tile 0 holds the widths on lane half 0 and the
-        // heights on half 1, so each half normalises its own 16 (squareplus,
-        // sum in order, quotients: the same operations per value) and one
-        // exchange per knot gives both halves both; tile 1's slopes (half 0)
-        // go to both halves.  Other ONE shapes exchange the whole row first.
-        constexpr bool kSplitWH = ONE && K == 16;
-        float P[NPV];
-#pragma unroll
-        for (int o = 0; o < TL; ++o)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            if constexpr (kSplitWH) {
-              if (o == 0) P[r] = pa[0][r];
-              else  // slope r of half 0, on both halves
-                P[2 * K + r] = x3_halves(pa[1][r]).lo;
-            } else if constexpr (ONE) {  // both halves end up with all of the dim's parameters
-              const X3Halves q = x3_halves(pa[o][r]);
-              P[32 * o + r] = q.lo;
-              P[32 * o + 16 + r] = q.hi;
-            } else {
-              P[16 * o + r] = pa[o][r];
-            }
-          }
-        X3M(11);
-#if ZF_X3_ABL == 10 || ZF_X3_ABL == 11  // tuning: 64 extra VALU (10: v_add, 11: v_exp) in the spline phase
-#pragma unroll
-        for (int q2 = 0; q2 < 64; ++q2) {
-          float dd;
-          if (ZF_X3_ABL == 10) asm volatile("v_add_f32 %0, %1, %2" : "=v"(dd) : "v"(pa[0][q2 & 15]), "v"(pa[1][q2 & 15]));
-          else asm volatile("v_exp_f32 %0, %1" : "=v"(dd) : "v"(pa[0][q2 & 15]));
-        }
-#endif
-        // normalize_spline_params (utils.py:37-62) + RQ spline (utils.py:65-250)
-        const int d = 2 * pr + hh;
-        const bool dact = d < dt;  // the upper half idles on an odd last dim
-        float ldv = 0.f;
-        {
-          float* xp = xs + wrap((dact ? d : 0) + rot, D) * 32 + s;
-          const float xv = *xp;
-#ifndef ZF_X3_BSEARCH
-#define ZF_X3_BSEARCH 0
-#endif
-          RqsBin bin;
-          bool binned = false;
-          if constexpr (ZF_X3_BSEARCH && !kSplitWH && !kPreSP && (K == 8 || K == 16 || K == 32 || K == 64)) {
-            if (klit) {  // the halving search takes unpadded knots only, not yet squareplus'd ones
-              bin = x3_bin<!INV, K, OACT, true>(xv, P, kc);
-              binned = true;
-            }
-          }
-          if (!binned) {
-            float w[K], hg[K];
-            const float bc = kc.c * kc.rnorm;
-            if constexpr (kSplitWH) {
-              float sw = 0.f;  // half 0: the widths' sum, half 1: the heights'
-#pragma unroll
-              for (int j = 0; j < K; ++j) {
-                w[j] = kPreSP ? P[j] : x3_squareplus2_t<OACT>(P[j]);
-                sw = sw + w[j];
-              }
-              const float a = rcp_refined(sw) * kc.rnorm;
-#pragma unroll
-              for (int j = 0; j < K; ++j) {
-                const X3Halves q = x3_halves(__builtin_fmaf(w[j], a, bc));
-                w[j] = q.lo;
-                hg[j] = q.hi;
-              }
-            } else {
-              float sx = 0.f, sy = 0.f;
-#pragma unroll
-              for (int j = 0; j < K; ++j) {  // squareplus + sums in order (utils.py:30-33)
-                w[j] = kPreSP ? P[j] : x3_squareplus2_t<OACT>(P[j]);
-                hg[j] = kPreSP ? P[K + j] : x3_squareplus2_t<OACT>(P[K + j]);
-                sx = sx + w[j];
-                sy = sy + hg[j];
-              }
-              // (v / sum + c) / (1 + c K) as one fma per knot (v and sum both
-              // 2*squareplus: the same quotient bits): the parameters
-              // themselves already differ from the reference's in the last ulp
-              // (GEMM summation order), so correctly rounded divisions buy nothing.
-              const float ax = rcp_refined(sx) * kc.rnorm, ay = rcp_refined(sy) * kc.rnorm;
-#pragma unroll
-              for (int j = 0; j < K; ++j) {
-                w[j] = __builtin_fmaf(w[j], ax, bc);
-                hg[j] = __builtin_fmaf(hg[j], ay, bc);
-              }
-            }
-            X3M(12);
-            float sl[K - 1];  // raw slope logits; the bin's two get squareplus'd
-#pragma unroll
-            for (int j = 0; j < K - 1; ++j) sl[j] = P[2 * K + j];
-#ifndef ZF_X3_EXECBIN
-#define ZF_X3_EXECBIN 1
-#endif
-            // the latch as exec-masked moves (rqs_bin_exec): -15% of the spline phase's VALU issue
-            const auto spf = [](float v) { return v == 0.f ? 1.f : x3_squareplus_t<OACT>(v); };
-            if constexpr (ZF_X3_EXECBIN && K % 8 == 0) bin = rqs_bin_exec<!INV, K>(xv, w, hg, sl, spf, padlast);
-            else bin = rqs_bin_monotone<!INV, K>(xv, w, hg, sl, spf, padlast);
-            X3M(13);
-          }
-          float yv;
-          if (!INV) {
-            float l;
-            x3_forward_eval(xv, bin, yv, l);
-            ldv = dact ? l : 0.f;
-          } else {
-            yv = rqs_inverse_eval(xv, bin);
-          }
-          if (dact) *xp = yv;
-        }
-        wave_lds_sync();
-        if (!INV) {
-          const X3Halves q = x3_halves(ldv);
-          ldn = ldn + q.lo;
-          if (2 * pr + 1 < dt) ldn = ldn + q.hi;
-        }
-      }
-      if (!INV) ld = ld + ldn;  // Chain: log_det += ld (bijectors.py:110)
-      X3T(5);
+      x3_nsc<NT, K, T, PAIRS, ONE, INV, OACT, ASET, false>(op, opc, x3, pipe, par, xs, rot, D, s, hh, lane, ld,
+                                                           tr);
     }
   }
 
@@ -1921,18 +2174,16 @@ __global__ __launch_bounds__(kX3Waves * 64, (x3_occupancy<T, K, PAIRS>())) void 
                     ld_out, s_part);
 #ifdef ZF_X3_TRACE
   X3T(6);
-  tacc[7] = pipe.tbar;
-  tacc[11] = pipe.tdma;
-  tacc[12] = pipe.tgrp;
-  tacc[8] = t_last - t_begin;
+  tr.tacc[7] = pipe.tbar;
+  tr.tacc[11] = pipe.tdma;
+  tr.tacc[12] = pipe.tgrp;
+  tr.tacc[8] = tr.t_last - t_begin;
   if (lane == 0 && x3_trace_buf != nullptr) {
     unsigned long long* o = x3_trace_buf + ((long long)blockIdx.x * NW + wave) * kX3TraceSlots;
 #pragma unroll
-    for (int k = 0; k < kX3TraceSlots; ++k) o[k] = tacc[k];
+    for (int k = 0; k < kX3TraceSlots; ++k) o[k] = tr.tacc[k];
   }
 #endif
-#undef X3T
-#undef X3M
 }
 
 template <int NT, int K, int T, bool PAIRS, bool ONE, bool OACT, int ASET = 0>
@@ -1978,6 +2229,9 @@ int launch_x3_k(const X3Launch& a, bool inverse) {
                : launch_x3<NT, K, 8, true, false, OACT, ASET>(a, inverse);
   return enotsup("split-MFMA kernel: hidden tiles not instantiated");
 }
+
+#undef X3T
+#undef X3M
 
 }  // namespace
 }  // namespace zf
