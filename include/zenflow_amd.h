@@ -337,6 +337,44 @@ int zf_trainer_loss_grad_shard(zf_trainer_t* trainer, const float* x, const floa
 int zf_trainer_step_shard(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows, int64_t global_rows,
                           double* loss, void* stream);
 
+/* Gradients with respect to the flow's inputs.  The reference's Flow is a
+ * differentiable JAX function (flow.py:22-48) and its users differentiate it
+ * with respect to x and c: examples/deep_set.ipynb's DeepSetFlow feeds
+ * c = phi(x) into self.flow(y, c, train=train), and jax.grad(loss_fn_2)
+ * trains phi together with the flow.
+ *
+ * Train mode (train.py:64-86): loss_grad / step as above, and gc (device,
+ * (rows, C), this rank's rows) = d loss / d c of the GLOBAL loss (scaled by
+ * 1 / global_rows), through BatchNorm on batch statistics (the global sums of
+ * the reverse pass).  The couplings accumulate in a fixed order: the last
+ * coupling assigns, earlier ones add.  gc == NULL or C == 0: exactly the
+ * entries above.  loss, grad and the stepped blob have the same bits with
+ * and without gc; step with gc launches the kernels eagerly (the captured
+ * step graph is the one of zf_trainer_step_shard, unchanged).  d loss / d x
+ * in train mode is not provided (ShiftBounds' batch min / max route gradient
+ * to the arg-extreme rows). */
+int zf_trainer_loss_grad_cond_shard(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows,
+                                    int64_t global_rows, int update_stats, double* loss, float* grad,
+                                    float* gc, void* stream);
+int zf_trainer_step_cond_shard(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows,
+                               int64_t global_rows, double* loss, float* gc, void* stream);
+
+/* Eval mode: the vector-Jacobian product of log_prob (flow.py:22-48 with
+ * train=False) at the trainer's current blob — BatchNorm on the stored
+ * mean / var, ShiftBounds on the stored xmin / xmax (no batch reductions, no
+ * communicator, no statistics update).  x (N,D), c (N,C) or NULL, cot (N,) or
+ * NULL (= ones); any of the outputs may be NULL:
+ *   log_prob (N,)  with flow.py:47's nan_to_num
+ *   gx (N,D)       gx[i] = cot[i] * d log_prob[i] / d x[i]
+ *   gc (N,C)       gc[i] = cot[i] * d log_prob[i] / d c[i]
+ * Rows whose log_prob is not finite before nan_to_num get all-zero gx and gc
+ * rows (the `where` gradient of nan_to_num).  Any N >= 1, processed in chunks
+ * of batch_max rows; rows are independent (a row's results depend on its own
+ * inputs and on the chunk's row count, which selects the GEMM kernels, only).
+ * The trainer's limits apply (ZF_ENOTSUP at zf_trainer_create). */
+int zf_trainer_log_prob_vjp(zf_trainer_t* trainer, const float* x, const float* c, const float* cot,
+                            float* log_prob, float* gx, float* gc, int64_t N, void* stream);
+
 /* Copy the trainer's natural blob (parameters + statistics) out / in. */
 int zf_trainer_get_blob(zf_trainer_t* trainer, float* blob_host);
 int zf_trainer_set_blob(zf_trainer_t* trainer, const float* blob_host);

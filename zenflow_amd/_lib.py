@@ -139,6 +139,9 @@ SIGNATURES = {
     "zf_trainer_set_comm": (_int, [_vp, _vp]),
     "zf_trainer_loss_grad_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
     "zf_trainer_step_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "zf_trainer_loss_grad_cond_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "zf_trainer_step_cond_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "zf_trainer_log_prob_vjp": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "zf_trainer_get_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_blob": (_int, [_vp, _vp]),
     "zf_latent_sample": (_int, [_int, _dbl, _u64, _vp, _i64, _int, _vp]),

@@ -3,6 +3,13 @@
 // optimiser update, for zenflow.train (src/zenflow/train.py:18-138):
 //   loss_fn  (train.py:64-72): -mean(Flow.__call__(x, c, train=True))
 //   step     (train.py:80-86): jax.grad -> optax (n)adamw update
+// and the gradients with respect to the flow's inputs, which the reference's
+// users take by differentiating Flow as a JAX function:
+//   train mode  d loss / d c (train.py:64-86 through c; the DeepSetFlow /
+//               loss_fn_2 cells of examples/deep_set.ipynb feed c = phi(x)
+//               into self.flow(y, c, train=train) and train phi with jax.grad)
+//   eval mode   the vector-Jacobian product of log_prob (flow.py:22-48) with
+//               respect to x and c (zf_trainer_log_prob_vjp)
 // The path is op by op and unfused (a training batch is 10^3-10^5 rows; the
 // weights change every step, so the fused inference kernels' packed weight
 // layouts would have to be rebuilt each step).  GEMMs are an LDS-tiled fp32
@@ -1608,12 +1615,15 @@ __global__ __launch_bounds__(kSplThreads) void spline_inv_kernel(const float* __
 // Reverse: g_in = dL/d(state_in) from g_out = dL/d(state_out) and gl per row;
 // conditioning columns pass g_out through (their MLP share is added later).
 // dL/dP is formed in place in the staged rows and written back coalesced.
-template <int KT>
+// ROWGL (the eval-mode vector-Jacobian product, where every row has its own
+// cotangent): gl of row b is glr[b]; otherwise the constant gl, as before.
+template <int KT, bool ROWGL = false>
 __global__ __launch_bounds__(kSplThreads) void spline_bwd_kernel(const float* __restrict__ s_in,
                                                                  const float* __restrict__ P,
                                                                  const float* __restrict__ g_out, float gl,
                                                                  float* __restrict__ g_in, float* __restrict__ gP,
-                                                                 int B, int D, int dt, int K, int rot) {
+                                                                 int B, int D, int dt, int K, int rot,
+                                                                 const float* __restrict__ glr = nullptr) {
   extern __shared__ float sp[];
   const int S = 3 * K - 1, rpb = kSplThreads / dt;
   const int lr = threadIdx.x / dt, d = threadIdx.x - lr * dt;
@@ -1623,6 +1633,8 @@ __global__ __launch_bounds__(kSplThreads) void spline_bwd_kernel(const float* __
   const bool ok = lr < nrows;
   const int col = pmodi(d + rot, D);
   const float xv = ok ? s_in[b * D + col] : 0.f, gv = ok ? g_out[b * D + col] : 0.f;  // in flight with the staging
+  float glv = gl;
+  if constexpr (ROWGL) glv = ok ? glr[b] : 0.f;
   stage_rows(sp, P + b0 * dt * S, n);
   __syncthreads();
   if (ok) {
@@ -1632,7 +1644,7 @@ __global__ __launch_bounds__(kSplThreads) void spline_bwd_kernel(const float* __
     }
     float y, ldv, gx;
     float* row = sp + threadIdx.x * S;
-    spline_one<true, KT>(row, K, xv, y, ldv, gv, gl, &gx, row);
+    spline_one<true, KT>(row, K, xv, y, ldv, gv, glv, &gx, row);
     g_in[b * D + col] = gx;
   }
   __syncthreads();
@@ -1703,7 +1715,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_small(const float* __restrict__ g
                                                      const float* __restrict__ scale, const float* __restrict__ rstd,
                                                      double* __restrict__ g_scale, double* __restrict__ g_bias,
                                                      float* __restrict__ g, int B, int D, int C, int dt, int dc,
-                                                     int rot, int n, int rows) {
+                                                     int rot, int n, int rows, float* __restrict__ gc = nullptr,
+                                                     int gc_assign = 0) {
   __shared__ double p1[kMaxLeaves * 64], p2[kMaxLeaves * 64];
   __shared__ float mg_s[64], mgu_s[64];
   const int DC = dc + C, tid = threadIdx.x;
@@ -1733,6 +1746,16 @@ __global__ __launch_bounds__(1024) void bn_bwd_small(const float* __restrict__ g
     float* gp = g + b * D + pmodi(dt + kk + rot, D);
     *gp = add_rn(*gp, gu);
   }
+  // the condition columns' share, d loss / d c (gather_gc_kernel's arithmetic)
+  if (gc) {
+    for (long long i = tid; i < (long long)B * C; i += 1024) {
+      const long long b = i / C;
+      const int kk = dc + (int)(i - b * C);
+      const long long e = b * DC + kk;
+      const float gu = bn_grad_in(gUbn[e], Uhat[e], scale[kk], rstd[kk], mg_s[kk], mgu_s[kk]);
+      gc[i] = gc_assign ? gu : add_rn(gc[i], gu);
+    }
+  }
 }
 
 __global__ void scatter_gu_kernel(const float* __restrict__ gU, float* __restrict__ g, int B, int D, int C, int dt,
@@ -1744,6 +1767,199 @@ __global__ void scatter_gu_kernel(const float* __restrict__ gU, float* __restric
   const int k = (int)(i - b * dc);
   float* gp = g + b * D + pmodi(dt + k + rot, D);
   *gp = add_rn(*gp, gU[b * DC + k]);
+}
+
+// The condition columns of gU = d loss / d U (columns dc .. dc + C) into
+// gc = d loss / d c: the coupling nearest the latent assigns, the ones before
+// it add in a fixed order (the reverse loop's), each add separately rounded.
+__global__ void gather_gc_kernel(const float* __restrict__ gU, float* __restrict__ gc, int B, int C, int dc,
+                                 int assign) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * C) return;
+  const long long b = i / C;
+  const float gu = gU[b * (dc + C) + dc + (int)(i - b * C)];
+  gc[i] = assign ? gu : add_rn(gc[i], gu);
+}
+
+// ---- eval-mode vector-Jacobian product of log_prob (flow.py:22-48) ----------
+// The same op-by-op chain with the stored statistics (BatchNorm mean / var,
+// ShiftBounds xmin / xmax): every row is independent, so there are no batch
+// reductions; the reverse pass carries a per-row cotangent ce = d (sum cot lp)
+// / d lp_row, zeroed on rows whose log_prob is not finite (the `where`
+// gradient of flow.py:47's nan_to_num), and yields d / d x and d / d c.
+
+// ShiftBounds with the stored xmin / xmax (bijectors.py:258-273, train=False),
+// first op of the chain (rot == 0): sets ld.
+__global__ void sb_eval_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ ld,
+                                   const float* __restrict__ sb, int B, int D) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float lds = 0.f;
+  for (int i = 0; i < D; ++i) {
+    const float v = x[(long long)b * D + i];
+    const float* r = sb + 8 * i;
+    const int mode = (int)r[0];
+    const float a = r[1], bb = r[2];
+    float z, l;
+    if (mode == ZF_SB_BOTH) {
+      const float mul = (float)(1.0 / ((double)bb - (double)a));
+      z = (v - a) * mul;
+      l = logf(mul);
+    } else {
+      const float xmin = r[3], xmax = r[4];
+      const float mul = 1.0f / (xmax - xmin);
+      float t = v;
+      if (mode == ZF_SB_LOWER) t = logf((v - a) + 1.17549435e-38f);
+      if (mode == ZF_SB_UPPER) t = logf((bb - v) + 1.17549435e-38f);
+      const float zr = (t - xmin) * mul;
+      z = (zr != zr) ? zr : fminf(fmaxf(zr, 0.f), 1.f);
+      l = (mode == ZF_SB_NONE) ? logf(mul) : logf(mul) - t;
+    }
+    lds = lds + l;
+    y[(long long)b * D + i] = z;
+  }
+  ld[b] = lds;
+}
+
+// Its reverse and the end of the chain's reverse pass: gx = g . dz/dx +
+// ce . d log_det / dx per dim (sb == NULL: no ShiftBounds, gx = g).
+//   BOTH  z = (x - a) mul                      -> g mul
+//   NONE  z = clip((x - xmin) mul, 0, 1)        -> g mul inside (0, 1), else 0
+//   LOWER / UPPER the same through t = safe_log(+-(x - a)), dt/dx =
+//         +-1 / (+-(x - a) + tiny), and log_det = log(mul) - t -> (.. - ce) dt/dx
+// A row with ce == 0 (log_prob not finite, or a zero cotangent) is written as
+// zeros whatever its intermediates hold.
+__global__ void sb_eval_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                   const float* __restrict__ ce, const float* __restrict__ sb,
+                                   float* __restrict__ gx, int B, int D) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)B * D) return;
+  const long long b = e / D;
+  const int i = (int)(e - b * D);
+  const float cb = ce[b];
+  float out = g[e];
+  if (sb) {
+    const float* r = sb + 8 * i;
+    const int mode = (int)r[0];
+    const float a = r[1], bb = r[2], v = x[e];
+    if (mode == ZF_SB_BOTH) {
+      out = out * (float)(1.0 / ((double)bb - (double)a));
+    } else {
+      const float xmin = r[3], xmax = r[4];
+      const float mul = 1.0f / (xmax - xmin);
+      float t = v, dtdx = 1.0f;
+      if (mode == ZF_SB_LOWER) {
+        const float w = (v - a) + 1.17549435e-38f;
+        t = logf(w);
+        dtdx = 1.0f / w;
+      }
+      if (mode == ZF_SB_UPPER) {
+        const float w = (bb - v) + 1.17549435e-38f;
+        t = logf(w);
+        dtdx = -1.0f / w;
+      }
+      const float zr = (t - xmin) * mul;
+      float gt = (zr > 0.f && zr < 1.f) ? out * mul : 0.f;
+      if (mode != ZF_SB_NONE) gt = gt - cb;
+      out = gt * dtdx;
+    }
+  }
+  gx[e] = cb == 0.f ? 0.f : out;
+}
+
+// U = hstack(xc, c) and BatchNorm with the stored statistics (flax,
+// use_running_average=True): Ubn = (u - mean) rsqrt(var + eps) scale + bias.
+// Row 0's threads also store rstd[k] = rsqrt(var + eps), all the reverse needs.
+__global__ void bn_eval_fwd_kernel(const float* __restrict__ s, const float* __restrict__ c,
+                                   const float* __restrict__ nat_bn, float* __restrict__ Ubn,
+                                   float* __restrict__ rstd_out, int B, int D, int C, int dt, int dc, int rot) {
+  const int DC = dc + C;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * DC) return;
+  const long long b = i / DC;
+  const int k = (int)(i - b * DC);
+  const float u = k < dc ? s[b * D + pmodi(dt + k + rot, D)] : c[b * C + (k - dc)];
+  const float rstd = 1.0f / sqrtf(nat_bn[DC + k] + kBnEps);
+  if (b == 0) rstd_out[k] = rstd;
+  Ubn[i] = bn_out(bn_hat(u, nat_bn[k], rstd), nat_bn[2 * DC + k], nat_bn[3 * DC + k]);
+}
+
+// Its reverse, gU = gUbn scale rstd, with the scatter fused: the dc state
+// columns are added into g (d / d state, as scatter_gu_kernel), the C
+// condition columns assigned to / added into gc (as gather_gc_kernel; gc may
+// be NULL).  Rows with ce == 0 contribute exact zeros.
+__global__ void bn_eval_bwd_kernel(const float* __restrict__ gUbn, const float* __restrict__ scale,
+                                   const float* __restrict__ rstd, const float* __restrict__ ce,
+                                   float* __restrict__ g, float* __restrict__ gc, int gc_assign, int B, int D, int C,
+                                   int dt, int dc, int rot) {
+#pragma clang fp contract(off)
+  const int DC = dc + C;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * DC) return;
+  const long long b = i / DC;
+  const int k = (int)(i - b * DC);
+  const float gu = ce[b] == 0.f ? 0.f : (gUbn[i] * scale[k]) * rstd[k];
+  if (k < dc) {
+    float* gp = g + b * D + pmodi(dt + k + rot, D);
+    *gp = *gp + gu;
+  } else if (gc) {
+    float* gp = gc + b * C + (k - dc);
+    *gp = gc_assign ? gu : *gp + gu;
+  }
+}
+
+// Latent log-density with a per-row cotangent (cot NULL: ones): lp_out =
+// nan_to_num(latent.log_prob(z) + ld) (flow.py:45-47; NULL: not wanted), ce =
+// cot where that sum is finite and 0 elsewhere, gz = ce . d latent_lp / dz —
+// latent_loss_kernel's densities and `fin` rule, the rule applied to the
+// log-det cotangent ce as well.
+__global__ __launch_bounds__(256) void latent_vjp_kernel(const float* __restrict__ z, const float* __restrict__ ld,
+                                                         const float* __restrict__ cot, int B, int D, int rot,
+                                                         int latent, float a, float betac, float tnmass,
+                                                         float* __restrict__ lp_out, float* __restrict__ ce,
+                                                         float* __restrict__ gz) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float lat = 0.f;
+  for (int j = 0; j < D; ++j) {
+    const float v = z[(long long)b * D + pmodi(j + rot, D)];
+    float t;
+    if (latent == ZF_LATENT_NORMAL || latent == ZF_LATENT_TRUNCNORM) {
+      const float dv = v - 0.5f;
+      t = (logf(6.28318530717958647692f * 0.01f) + (dv * dv) / 0.01f) / -2.0f;
+      if (latent == ZF_LATENT_TRUNCNORM) {
+        t = t - tnmass;
+        if (dv / 0.1f < -5.f || dv / 0.1f > 5.f) t = -INFINITY;
+      }
+    } else if (latent == ZF_LATENT_BETA) {
+      const float am1 = a - 1.0f;
+      t = betac + (am1 == 0.f ? 0.f : am1 * logf(v)) + (am1 == 0.f ? 0.f : am1 * log1pf(-v));
+      if (v > 1.f || v < 0.f) t = -INFINITY;
+    } else if (latent == ZF_LATENT_UNIFORM) {
+      t = (v > 1.f || v < 0.f) ? -INFINITY : 0.f;
+    } else {
+      t = 0.f;
+    }
+    lat = lat + t;
+  }
+  float lp = lat + ld[b];
+  const bool fin = (lp == lp) && lp != INFINITY && lp != -INFINITY;
+  if (lp != lp) lp = -INFINITY;
+  if (lp == INFINITY) lp = 3.40282347e38f;
+  if (lp == -INFINITY) lp = -3.40282347e38f;
+  if (lp_out) lp_out[b] = lp;
+  const float s = fin ? (cot ? cot[b] : 1.0f) : 0.f;
+  ce[b] = s;
+  for (int j = 0; j < D; ++j) {
+    const int col = pmodi(j + rot, D);
+    const float v = z[(long long)b * D + col];
+    float g = 0.f;
+    if (s != 0.f) {
+      if (latent == ZF_LATENT_NORMAL || latent == ZF_LATENT_TRUNCNORM) g = -(v - 0.5f) / 0.01f;
+      else if (latent == ZF_LATENT_BETA) g = (a - 1.0f) / v - (a - 1.0f) / (1.0f - v);
+    }
+    gz[(long long)b * D + col] = s * g;
+  }
 }
 
 // ---- latent + loss ------------------------------------------------------------
@@ -1913,6 +2129,7 @@ struct zf_trainer {
   float* d_g0 = nullptr;      // [bmax][D]
   float* d_g1 = nullptr;
   float* d_small = nullptr;   // per-column scratch (ShiftBounds min / max)
+  float* d_ce = nullptr;      // [bmax] per-row cotangent of the eval-mode VJP
   double* d_leaf = nullptr;   // leaf partials of the BatchNorm sums / loss [kLeafCap][128]
   double* d_leaf2 = nullptr;  // first-level tree roots [kLeafCap / 64][128]
   double* d_ws2 = nullptr;    // first-level roots of the split-K partials
@@ -2010,6 +2227,7 @@ int zf_trainer_create(const zf_flow_desc* desc_in, const float* blob_host, int64
   t->d_g0 = zf::dmalloc(t, B * D, rc);
   t->d_g1 = zf::dmalloc(t, B * D, rc);
   t->d_small = zf::dmalloc(t, 8 * 256, rc);
+  t->d_ce = zf::dmalloc(t, B, rc);
   t->d_leaf = (double*)zf::dmalloc(t, 2 * zf::kLeafCap * 128, rc);
   t->d_leaf2 = (double*)zf::dmalloc(t, 2 * (zf::kLeafCap / zf::kMaxLeaves) * 128, rc);
   t->d_ws2 = (double*)zf::dmalloc(t, 2 * (zf::kWsFloats / zf::kMaxLeaves), rc);
@@ -2149,8 +2367,13 @@ int dp_combine(zf_trainer_t* t, double* roots, long long n, hipStream_t st) {
 // loss_slot(t), the gradient in G (natural blob layout, fp32).
 // step_in_cast: an optimiser update follows; the one-device gradient cast
 // advances its step counter (trainer_update then skips step_kernel).
+// gc (this rank's (B, C) rows, or NULL): also d loss / d c, the condition
+// columns of every coupling's d loss / d U (train.py:64-86 differentiated
+// with respect to the conditions, as jax.grad(loss_fn_2) of
+// examples/deep_set.ipynb does through DeepSetFlow's c = phi(x)).  It only
+// adds stores: loss, G and the stepped blob keep their bits.
 int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* G, hipStream_t st,
-                 bool* step_in_cast = nullptr) {
+                 bool* step_in_cast = nullptr, float* gc = nullptr) {
   const int D = t->D, C = t->C, W = t->comm.world;
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
@@ -2283,6 +2506,8 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
   zf::WgradQueue wq;
   wq.tb.count = 0;
   wq.gq.count = 0;
+  if (C == 0) gc = nullptr;
+  int gc_assign = 1;  // the first coupling met (the last of the chain) assigns gc
   for (int i = desc.n_ops - 1; i >= 0; --i) {
     const zf_op_desc& op = desc.ops[i];
     if (op.kind == ZF_OP_ROLL || op.kind == ZF_OP_SHIFT_BOUNDS) continue;  // Roll: index map; SB: first op
@@ -2331,7 +2556,7 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
     double* gbn = G64 + op.off_bn;
     if (small_ok && (long long)B * DC <= zf::kBnSmall) {
       hipLaunchKernelGGL(zf::bn_bwd_small, dim3(1), dim3(1024), 0, st, nb.gU, nb.Uhat, bn + 2 * DC, nb.rstd,
-                         gbn + 2 * DC, gbn + 3 * DC, g_prev, B, D, C, dt, dc, r, lbn.n, lbn.rows);
+                         gbn + 2 * DC, gbn + 3 * DC, g_prev, B, D, C, dt, dc, r, lbn.n, lbn.rows, gc, gc_assign);
       ZF_CHECK_LAUNCH("bn_bwd_small");
     } else {
       // sums of gUbn and gUbn * Uhat: leaves -> tree (this rank's share of the
@@ -2350,12 +2575,20 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
       hipLaunchKernelGGL(zf::scatter_gu_kernel, dim3(zf::blocks_for((int64_t)B * dc)), dim3(256), 0, st, nb.gU,
                          g_prev, B, D, C, dt, dc, r);
       ZF_CHECK_LAUNCH("scatter_gu_kernel");
+      if (gc) {
+        hipLaunchKernelGGL(zf::gather_gc_kernel, dim3(zf::blocks_for((int64_t)B * C)), dim3(256), 0, st, nb.gU, gc, B,
+                           C, dc, gc_assign);
+        ZF_CHECK_LAUNCH("gather_gc_kernel");
+      }
     }
+    gc_assign = 0;
     float* tmp = g;
     g = g_prev;
     g_prev = tmp;
   }
   if ((rc = zf::wgrad_flush(wq, st))) return rc;
+  if (gc && gc_assign)  // no coupling: the loss does not depend on c
+    ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * C * sizeof(float), st));
   // ---- the gradient: (all ranks' fp64 shares, tree over ranks) -> fp32 ----
   if (W > 1) {
     rc = t->comm.allgather(t->comm.ctx, G64, t->d_gath, (size_t)t->nat_floats * sizeof(double), st);
@@ -2384,6 +2617,136 @@ int trainer_update(zf_trainer_t* t, hipStream_t st, bool step_done = false) {
                      t->d_v, t->d_mask, (long long)t->nat_floats, o.learning_rate, o.b1, o.b2, o.eps, o.weight_decay,
                      o.nesterov, t->d_bc);
   ZF_CHECK_LAUNCH("adam_kernel");
+  return ZF_OK;
+}
+
+// Eval-mode forward with stored activations and the reverse pass for one
+// chunk of B <= bmax rows (zf_trainer_log_prob_vjp): the trainer's GEMMs and
+// spline kernels, none of its batch reductions, weight-gradient GEMMs, fp64
+// accumulators or optimiser.  The GEMM forms follow the chunk's row count
+// (never the other rows' values): a row's bits depend on its own inputs and
+// on how many rows share the chunk only.
+int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const float* cot, float* lp_out, float* gx,
+                      float* gc, int B, hipStream_t st) {
+  int rc = trainer_stage(t, x, c_in, B, st);
+  if (rc) return rc;
+  const int D = t->D, C = t->C;
+  const float* c = t->d_c;
+  const zf_flow_desc& desc = t->desc;
+  float* nat = t->d_nat;
+  std::vector<float*> sp(desc.n_ops + 1);
+  sp[0] = t->d_state;
+  for (int i = 0; i < desc.n_ops; ++i)
+    sp[i + 1] = desc.ops[i].kind == ZF_OP_ROLL ? sp[i] : t->d_state + (int64_t)(i + 1) * t->bmax * D;
+  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
+  if (!sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
+  // ---- forward (eval mode) ----
+  int rot = 0;
+  std::vector<int> rots(desc.n_ops + 1, 0);
+  for (int i = 0; i < desc.n_ops; ++i) {
+    const zf_op_desc& op = desc.ops[i];
+    rots[i] = rot;
+    float* sin = sp[i];
+    float* sout = sp[i + 1];
+    if (op.kind == ZF_OP_ROLL) {
+      rot = pmodi(rot - op.shift, D);
+    } else if (op.kind == ZF_OP_SHIFT_BOUNDS) {  // i == 0 (zf_trainer_create)
+      hipLaunchKernelGGL(sb_eval_fwd_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sin, sout, t->d_ld,
+                         (const float*)(nat + op.off_sb), B, D);
+      ZF_CHECK_LAUNCH("sb_eval_fwd_kernel");
+    } else if (op.kind == ZF_OP_NSC) {
+      int dt, dc, DC, S;
+      nsc_dims(t, op, dt, dc, DC, S);
+      zf_trainer::NscBufs& nb = t->nsc[i];
+      hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
+                         (const float*)(nat + op.off_bn), nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
+      ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
+      const float* in = nb.Ubn;
+      int in_w = DC;
+      for (int l = 0; l <= op.n_hidden; ++l) {
+        const bool last = (l == op.n_hidden);
+        const int out_w = last ? dt * S : op.hidden[l];
+        rc = gemm(false, B, B, out_w, in_w, in, in_w, nat + op.off_w[l], out_w, last ? nb.P : nb.Z[l], out_w, st,
+                  kEpiBias, nat + op.off_b[l], last ? nullptr : nb.H[l], nullptr, op.act,
+                  t->splitq ? t->d_split : nullptr, kSplitFloats);
+        if (rc) return rc;
+        if (!last) {
+          in = nb.H[l];
+          in_w = out_w;
+        }
+      }
+      const int rpb = kSplThreads / dt;
+#define ZF_SPL(KTV) hipLaunchKernelGGL((spline_fwd_kernel<KTV>), dim3(blocks_for(B, rpb)), dim3(kSplThreads),\
+                         (size_t)kSplThreads * S * sizeof(float), st, sin, sout, nb.P, t->d_ld, B, D, dt, op.knots, rot)
+      ZF_KNOT_DISPATCH(op.knots, ZF_SPL);
+#undef ZF_SPL
+      ZF_CHECK_LAUNCH("spline_fwd_kernel");
+    } else {
+      return einval("op %d: unknown kind", i);
+    }
+  }
+  // ---- latent, log_prob, the per-row cotangent ----
+  const int lt = desc.latent;
+  const float a = (float)desc.latent_param;
+  const float betac = lt == ZF_LATENT_BETA
+                          ? (float)(-(std::lgamma(desc.latent_param) * 2.0 - std::lgamma(2.0 * desc.latent_param)))
+                          : 0.f;
+  const float tnm = (float)std::log1p(-2.0 * 0.5 * std::erfc(5.0 / std::sqrt(2.0)));
+  float* g = t->d_g0;
+  float* g_prev = t->d_g1;
+  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, cot, B, D, rot,
+                     lt, a, betac, tnm, lp_out, t->d_ce, g);
+  ZF_CHECK_LAUNCH("latent_vjp_kernel");
+  if (!gx && !gc) return ZF_OK;
+  // ---- reverse ----
+  int gc_assign = 1;
+  for (int i = desc.n_ops - 1; i >= 0; --i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind != ZF_OP_NSC) continue;  // Roll: index map; ShiftBounds (first op): below
+    int dt, dc, DC, S;
+    nsc_dims(t, op, dt, dc, DC, S);
+    zf_trainer::NscBufs& nb = t->nsc[i];
+    const int r = rots[i];
+    const int rpb = kSplThreads / dt;
+#define ZF_SPL(KTV) hipLaunchKernelGGL((spline_bwd_kernel<KTV, true>), dim3(blocks_for(B, rpb)), dim3(kSplThreads),\
+                       (size_t)kSplThreads * S * sizeof(float), st, sp[i], nb.P, g, 0.f, g_prev, nb.gP, B, D, dt,\
+                       op.knots, r, (const float*)t->d_ce)
+    ZF_KNOT_DISPATCH(op.knots, ZF_SPL);
+#undef ZF_SPL
+    ZF_CHECK_LAUNCH("spline_bwd_kernel<rowgl>");
+    const float* gout = nb.gP;
+    int out_w = dt * S;
+    float* gbufs[2] = {nb.gA, nb.gB};
+    int which = 0;
+    for (int l = op.n_hidden; l >= 0; --l) {
+      const int in_w = l == 0 ? DC : op.hidden[l - 1];
+      float* gin = l == 0 ? nb.gU : gbufs[which];
+      rc = gemm(true, B, B, in_w, out_w, gout, out_w, nat + op.off_w[l], out_w, gin, in_w, st,
+                l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? nb.Z[l - 1] : nullptr, op.act,
+                t->splitq ? t->d_split : nullptr, kSplitFloats);
+      if (rc) return rc;
+      if (l > 0) {
+        gout = gin;
+        out_w = in_w;
+        which ^= 1;
+      }
+    }
+    const float* bn = nat + op.off_bn;
+    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
+                       bn + 2 * DC, (const float*)nb.rstd, (const float*)t->d_ce, g_prev, gc, gc_assign, B, D, C, dt,
+                       dc, r);
+    ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
+    gc_assign = 0;
+    std::swap(g, g_prev);
+  }
+  if (gc && gc_assign)  // no coupling: log_prob does not depend on c
+    ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * C * sizeof(float), st));
+  if (gx) {
+    hipLaunchKernelGGL(sb_eval_bwd_kernel, dim3(blocks_for((int64_t)B * D)), dim3(256), 0, st,
+                       (const float*)t->d_state, (const float*)g, (const float*)t->d_ce,
+                       sb_first ? (const float*)(nat + desc.ops[0].off_sb) : nullptr, gx, B, D);
+    ZF_CHECK_LAUNCH("sb_eval_bwd_kernel");
+  }
   return ZF_OK;
 }
 
@@ -2437,6 +2800,23 @@ int zf_trainer_loss_grad_shard(zf_trainer_t* t, const float* x, const float* c, 
   return ZF_OK;
 }
 
+int zf_trainer_loss_grad_cond_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows,
+                                    int64_t global_rows, int update_stats, double* loss, float* grad, float* gc,
+                                    void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (!gc || t->C == 0)
+    return zf_trainer_loss_grad_shard(t, x, c, rows, global_rows, update_stats, loss, grad, stream);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = zf::trainer_stage(t, x, c, rows, st);
+  if (rc) return rc;
+  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
+    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
+  rc = zf::trainer_body(t, (int)rows, global_rows, update_stats, grad ? grad : t->d_grad, st, nullptr, gc);
+  if (rc) return rc;
+  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
+  return ZF_OK;
+}
+
 int zf_trainer_loss_grad(zf_trainer_t* t, const float* x, const float* c, int64_t B, int update_stats,
                          double* loss, float* grad, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
@@ -2463,6 +2843,46 @@ int zf_trainer_step_shard(zf_trainer_t* t, const float* x, const float* c, int64
   }
   t->t += 1;
   if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
+  return ZF_OK;
+}
+
+// With gc the step is launched eagerly (the captured step graph stays as it
+// is and writes no gc): the same kernels in the same order, so the same bits
+// (tests/test_gpu_train.py::test_step_graph_matches_eager).
+int zf_trainer_step_cond_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows,
+                               double* loss, float* gc, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (!gc || t->C == 0) return zf_trainer_step_shard(t, x, c, rows, global_rows, loss, stream);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = zf::trainer_stage(t, x, c, rows, st);
+  if (rc) return rc;
+  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
+    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
+  bool stepped = false;
+  rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, &stepped, gc);
+  if (!rc) rc = zf::trainer_update(t, st, stepped);
+  if (rc) return rc;
+  t->t += 1;
+  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
+  return ZF_OK;
+}
+
+int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, const float* cot, float* log_prob,
+                            float* gx, float* gc, int64_t N, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (N < 1) return zf::einval("N must be at least 1");
+  if (!x) return zf::einval("x is NULL");
+  if (t->C > 0 && !c) return zf::einval("flow is conditional but c is NULL");
+  if (t->desc.latent == ZF_LATENT_NONE) return zf::einval("flow has no latent distribution");
+  hipStream_t st = (hipStream_t)stream;
+  const int D = t->D, C = t->C;
+  for (int64_t off = 0; off < N; off += t->bmax) {
+    const int B = (int)std::min<int64_t>(t->bmax, N - off);
+    const int rc = zf::trainer_vjp_chunk(t, x + off * D, C > 0 ? c + off * C : nullptr, cot ? cot + off : nullptr,
+                                         log_prob ? log_prob + off : nullptr, gx ? gx + off * D : nullptr,
+                                         gc && C > 0 ? gc + off * C : nullptr, B, st);
+    if (rc) return rc;
+  }
   return ZF_OK;
 }
 

@@ -295,6 +295,21 @@ class Program:
             N, L.stream()), "zf_flow_log_prob")
         return lp
 
+    # -- input gradients ---------------------------------------------------------
+    def vjp_handle(self, chunk_rows: int):
+        """The device handle of ``log_prob_and_grad`` (a trainer on this
+        program's blob, whose eval-mode reverse pass it runs), kept on the
+        program and re-created when ``chunk_rows`` grows.  The trainer's
+        limits (ShiftBounds first only, knots <= 64, at most 64 conditioner
+        inputs) raise NotImplementedError here."""
+        h = getattr(self, "_vjp", None)
+        if h is None or h.batch_max < chunk_rows:
+            from .train import Trainer
+
+            self._vjp = None  # release the smaller arena first
+            h = self._vjp = Trainer.for_program(self, int(chunk_rows))
+        return h
+
     # -- train mode --------------------------------------------------------------
     def colstats(self, x: DeviceArray, ncols, ld, col_offset, modes=None, params=None):
         N = x.shape[0]

@@ -57,6 +57,43 @@ class Flow(Module):
             lp = prog.log_prob(xd, cd)
         return lp if x_dev else lp.numpy()
 
+    def log_prob_and_grad(self, x, c=None, *, cotangent=None, chunk_rows: Optional[int] = None):
+        """``(log_prob, dx, dc)``: the eval-mode log_prob (flow.py:22-48) and
+        its vector-Jacobian product, ``dx[i] = cotangent[i] * d log_prob[i] /
+        d x[i]`` and likewise ``dc`` (None for an unconditional flow) — what
+        ``jax.vjp`` / ``jax.grad`` of the reference's ``flow.apply`` give with
+        respect to its inputs (the score for Langevin / HMC, the sensitivity
+        to a condition).  ``cotangent`` defaults to ones.  Rows whose log_prob
+        is not finite get zero gradient rows (nan_to_num's gradient).  Host
+        arrays in, host arrays out; DeviceArray in, DeviceArray out.  Rows
+        are processed ``chunk_rows`` (default ``min(N, 65536)``) at a time."""
+        scope = scope_for(self)
+        if scope.initializing:
+            shape = np.shape(x) if not isinstance(x, L.DeviceArray) else x.shape
+            if len(shape) != 2:
+                raise ValueError(f"x must be 2-D (N, D), got {shape}")
+            from .bijectors import _c_dims
+
+            C = _c_dims(c)
+            scope.init_module(self, int(shape[1]), C)
+            return (np.zeros(shape[0], np.float32), np.zeros(shape, np.float32),
+                    np.zeros((shape[0], C), np.float32) if C else None)
+        xd, x_dev = L.as_device(x)
+        if xd.ndim != 2:
+            raise ValueError(f"x must be 2-D (N, D), got {xd.shape}")
+        cd, _ = _prep_c(c)
+        if self.latent._dim is None:
+            self.latent._dim = xd.shape[1]
+        prog = self._program(scope.variables, xd.shape[1], 0 if cd is None else cd.shape[1])
+        cot = None
+        if cotangent is not None:
+            cot, _ = L.as_device(cotangent if isinstance(cotangent, L.DeviceArray)
+                                 else np.asarray(cotangent, np.float32).reshape(-1))
+        lp, dx, dc = BoundFlow(prog).log_prob_and_grad(xd, cd, cot, chunk_rows=chunk_rows)
+        if x_dev:
+            return lp, dx, dc
+        return lp.numpy(), dx.numpy(), None if dc is None else dc.numpy()
+
     def sample(self, conditions_or_size: Union[Any, int], *, seed: int = 0):
         """Samples from the learned distribution (flow.py:50-78): latent draw,
         then the bijector inverse on the GPU."""
@@ -148,3 +185,12 @@ class BoundFlow:
 
     def forward(self, x: L.DeviceArray, c: Optional[L.DeviceArray] = None):
         return self.program.forward(x, c)
+
+    def log_prob_and_grad(self, x: L.DeviceArray, c: Optional[L.DeviceArray] = None,
+                          cotangent: Optional[L.DeviceArray] = None, *, chunk_rows: Optional[int] = None):
+        """Eval-mode ``(log_prob, dx, dc)`` (``Flow.log_prob_and_grad``),
+        device in, device out."""
+        self.program._check_x(x)
+        N = x.shape[0]
+        rows = int(chunk_rows) if chunk_rows is not None else min(N, 65536)
+        return self.program.vjp_handle(max(1, rows)).log_prob_vjp(x, c if self.program.C else None, cotangent)

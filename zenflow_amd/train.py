@@ -80,8 +80,22 @@ class Trainer:
         self.D, self.C = int(D), int(C)
         self.batch_max = int(batch_max)
         self.optimizer = optimizer or DEFAULT_OPTIMIZER()
-        self.program = flow._program(variables, self.D, self.C)
-        prog = self.program
+        self._open(flow._program(variables, self.D, self.C), comm)
+
+    @classmethod
+    def for_program(cls, program, batch_max: int) -> "Trainer":
+        """A trainer on an existing device program's blob (the handle behind
+        ``Flow.log_prob_and_grad``; it keeps no reference to the program)."""
+        self = cls.__new__(cls)
+        self.flow = None
+        self.D, self.C = program.D, program.C
+        self.batch_max = int(batch_max)
+        self.optimizer = DEFAULT_OPTIMIZER()
+        self._open(program, None, keep_program=False)
+        return self
+
+    def _open(self, prog, comm, keep_program: bool = True):
+        self.program = prog if keep_program else None
         opt = self.optimizer.desc()
         h = ct.c_void_p()
         check(L.load_library().zf_trainer_create(
@@ -116,25 +130,77 @@ class Trainer:
         return int(global_rows) if global_rows is not None else int(rows) * self.world
 
     def loss_grad(self, x, c=None, update_stats: bool = False,
-                  global_rows: Optional[int] = None) -> Tuple[float, np.ndarray]:
+                  global_rows: Optional[int] = None, cond_grad: bool = False):
         """(loss, gradient in the natural blob layout) — loss_fn + jax.grad.
         Data parallel: ``x`` is this rank's shard of a global batch of
-        ``global_rows`` rows (default: equal shards); both results are global."""
+        ``global_rows`` rows (default: equal shards); both results are global.
+
+        ``cond_grad=True`` returns ``(loss, grad, gc)`` with ``gc`` (rows, C) =
+        d loss / d c of this rank's rows — what ``jax.grad(loss_fn_2)`` of
+        examples/deep_set.ipynb sends back into ``phi`` through
+        ``c = phi(x)``; a DeviceArray when ``c`` was one.  loss and grad have
+        the same bits either way."""
         xd, cd = self._dev(x, self.D), self._dev(c, self.C)
         g = DeviceArray((self.program.blob.size,))
-        check(L.load_library().zf_trainer_loss_grad_shard(
-            self.handle, xd.ptr, None if cd is None else cd.ptr, xd.shape[0], self._global(xd.shape[0], global_rows),
-            1 if update_stats else 0, self._loss.ptr, g.ptr, L.stream()), "zf_trainer_loss_grad")
-        self._last_rows = self._global(xd.shape[0], global_rows)
-        return self._fp32_mean(float(self._loss.numpy()[0])), g.numpy()
+        rows = xd.shape[0]
+        if cond_grad:
+            gc = self._gc_out(rows)
+            check(L.load_library().zf_trainer_loss_grad_cond_shard(
+                self.handle, xd.ptr, cd.ptr, rows, self._global(rows, global_rows),
+                1 if update_stats else 0, self._loss.ptr, g.ptr, gc.ptr, L.stream()), "zf_trainer_loss_grad_cond")
+        else:
+            check(L.load_library().zf_trainer_loss_grad_shard(
+                self.handle, xd.ptr, None if cd is None else cd.ptr, rows, self._global(rows, global_rows),
+                1 if update_stats else 0, self._loss.ptr, g.ptr, L.stream()), "zf_trainer_loss_grad")
+        self._last_rows = self._global(rows, global_rows)
+        loss = self._fp32_mean(float(self._loss.numpy()[0]))
+        if cond_grad:
+            return loss, g.numpy(), (gc if isinstance(c, DeviceArray) else gc.numpy())
+        return loss, g.numpy()
+
+    def _gc_out(self, rows: int) -> DeviceArray:
+        if self.C == 0:
+            raise ValueError("cond_grad=True needs a conditional flow (C > 0)")
+        return DeviceArray((rows, self.C))
 
     def grad_tree(self, grad_blob: np.ndarray) -> Dict[str, Any]:
         """Gradient blob -> FLAX ``params`` tree (like jax.grad's output)."""
         return {"bijector": self.program.blob_to_variables(grad_blob)["params"]}
 
-    def step(self, x, c=None, global_rows: Optional[int] = None) -> None:
+    def step(self, x, c=None, global_rows: Optional[int] = None, cond_grad: bool = False):
+        """One optimiser step (train.py:80-86).  ``cond_grad=True`` returns
+        ``gc`` (rows, C) = d loss / d c of the loss this step descended (a
+        DeviceArray when ``c`` was one); the stepped parameters have the same
+        bits either way."""
         xd, cd = self._dev(x, self.D), self._dev(c, self.C)
-        self._step_rows(xd.ptr, None if cd is None else cd.ptr, xd.shape[0], global_rows)
+        if not cond_grad:
+            self._step_rows(xd.ptr, None if cd is None else cd.ptr, xd.shape[0], global_rows)
+            return None
+        rows = xd.shape[0]
+        gc = self._gc_out(rows)
+        self._last_rows = self._global(rows, global_rows)
+        check(L.load_library().zf_trainer_step_cond_shard(self.handle, xd.ptr, cd.ptr, rows,
+                                                          self._global(rows, global_rows), self._loss.ptr, gc.ptr,
+                                                          L.stream()), "zf_trainer_step_cond")
+        return gc if isinstance(c, DeviceArray) else gc.numpy()
+
+    def log_prob_vjp(self, x: DeviceArray, c: Optional[DeviceArray] = None, cotangent: Optional[DeviceArray] = None):
+        """Eval-mode ``(log_prob, dx, dc)`` at the trainer's current
+        parameters and statistics (zf_trainer_log_prob_vjp): device in,
+        device out; ``dc`` is None for an unconditional flow."""
+        N = x.shape[0]
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError(f"x must have shape (N, {self.D}), got {x.shape}")
+        if self.C and (c is None or c.shape != (N, self.C)):
+            raise ValueError(f"this flow is conditional: c must have shape ({N}, {self.C})")
+        if cotangent is not None and int(np.prod(cotangent.shape)) != N:
+            raise ValueError(f"cotangent must have {N} entries, got shape {cotangent.shape}")
+        lp, dx = DeviceArray((N,)), DeviceArray((N, self.D))
+        dc = DeviceArray((N, self.C)) if self.C else None
+        check(L.load_library().zf_trainer_log_prob_vjp(
+            self.handle, x.ptr, c.ptr if self.C else None, None if cotangent is None else cotangent.ptr, lp.ptr,
+            dx.ptr, None if dc is None else dc.ptr, N, L.stream()), "zf_trainer_log_prob_vjp")
+        return lp, dx, dc
 
     def _step_rows(self, xptr: int, cptr: Optional[int], rows: int, global_rows: Optional[int] = None) -> None:
         """One step on ``rows`` device-resident rows (raw pointers; async)."""
