@@ -85,6 +85,10 @@ CONFIGS = {
     # output row maxima then come from the standalone row-max kernel for the
     # f16x2 last layer (zf_layered.hip)
     "h260": dict(D=3, C=0, K=8, layers=(260, 264), latent="normal"),
+    # ShiftBounds(bounds=...): a lower-bounded, an upper-bounded and a two-sided
+    # dim (bijectors.py:163-208); inputs and stored statistics from bounded_case
+    "bounded": dict(D=3, C=1, K=8, layers=(64, 64), latent="normal",
+                    bounds=((0, 0.0, None), (1, None, 2.0), (2, -1.0, 1.0))),
 }
 LAYERED = ["h512", "h384c2", "h1024k5", "h260"]
 ACTS = ["relu", "gelu", "tanh", "softplus", "sigmoid", "elu", "leaky_relu", "mixed", "mixed_fp32"]
@@ -148,6 +152,8 @@ def make_case(name, N=4096, seed=0, bias_scale=0.3):
     train-mode pass (margin 0.1) so some eval rows clip."""
     from oracle import zf_oracle as O
 
+    if name == "bounded":
+        return bounded_case(N, seed)
     cfg = dict(CONFIGS[name])
     rng = np.random.default_rng(seed)
     spec, variables = make_variables(cfg, rng, bias_scale)
@@ -158,6 +164,28 @@ def make_case(name, N=4096, seed=0, bias_scale=0.3):
     c = rng.standard_normal((N, cfg["C"])).astype(np.float32) if cfg["C"] else None
     model = {"bijector": spec, "latent": {"type": cfg["latent"]}}
     return {"cfg": cfg, "model": model, "variables": variables, "x": x, "c": c, "name": name}
+
+
+def bounded_case(N=256, seed=21):
+    """``make_case("bounded")``: D = 3 with a lower-bounded, an upper-bounded
+    and a two-sided dim; the stored xmin / xmax come from a separate, smaller
+    draw, so some rows clip."""
+    from oracle import zf_oracle as O
+
+    cfg = dict(CONFIGS["bounded"])
+    rng = np.random.default_rng(seed)
+    spec, variables = make_variables(cfg, rng)
+
+    def draw(n):
+        g = rng.standard_normal((n, 3))
+        return np.stack([np.exp(g[:, 0]), 2 - np.exp(g[:, 1]), np.tanh(g[:, 2])], axis=1).astype(np.float32)
+
+    _, _, sb = O.shift_bounds_forward(spec["bijectors"][0], {}, draw(64), train=True)
+    variables["batch_stats"]["bijector"]["bijectors_0"] = {k: np.asarray(v, np.float32) for k, v in sb.items()}
+    x = draw(N)
+    c = rng.standard_normal((N, 1)).astype(np.float32)
+    model = {"bijector": spec, "latent": {"type": "normal"}}
+    return {"cfg": cfg, "model": model, "variables": variables, "x": x, "c": c, "name": "bounded"}
 
 
 def build_flow(cfg):

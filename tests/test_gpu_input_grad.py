@@ -30,8 +30,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from oracle import zf_oracle as O
-from tests.flowcases import build_flow, make_case, make_variables
+from tests.flowcases import bounded_case as _bounded_case
+from tests.flowcases import build_flow, make_case
 from tests.input_grad_oracle import pack_job
 
 pytestmark = pytest.mark.gpu
@@ -140,26 +140,6 @@ EVAL_CASES = [("small", 256, 1), ("cfg2", 256, 2), ("cfg4", 256, 3), ("odd", 300
 def test_eval_vjp_parity(name, N, seed):
     case, ref = case_oracle(name, N, seed)
     check_eval(f"{name}/N={N}", case, ref, *gpu_vjp(case))
-
-
-def _bounded_case(N=256, seed=21):
-    """D = 3 with a lower-bounded, an upper-bounded and a two-sided dim; the
-    stored xmin / xmax come from a separate, smaller draw, so some rows clip."""
-    bounds = ((0, 0.0, None), (1, None, 2.0), (2, -1.0, 1.0))
-    cfg = dict(D=3, C=1, K=8, layers=(64, 64), latent="normal", bounds=bounds)
-    rng = np.random.default_rng(seed)
-    spec, variables = make_variables(cfg, rng)
-
-    def draw(n):
-        g = rng.standard_normal((n, 3))
-        return np.stack([np.exp(g[:, 0]), 2 - np.exp(g[:, 1]), np.tanh(g[:, 2])], axis=1).astype(F32)
-
-    _, _, sb = O.shift_bounds_forward(spec["bijectors"][0], {}, draw(64), train=True)
-    variables["batch_stats"]["bijector"]["bijectors_0"] = {k: np.asarray(v, F32) for k, v in sb.items()}
-    x = draw(N)
-    c = rng.standard_normal((N, 1)).astype(F32)
-    model = {"bijector": spec, "latent": {"type": "normal"}}
-    return {"cfg": cfg, "model": model, "variables": variables, "x": x, "c": c, "name": "bounded"}
 
 
 def test_bounded_shift_bounds():

@@ -1254,9 +1254,19 @@ __device__ __forceinline__ void bn_stats_one(double sum, double sumsq, long long
                                              float* __restrict__ nat_bn, float& mean, float& rstd, int update) {
 #pragma clang fp contract(off)
   // every operation separately rounded: the same bits in every kernel that inlines this
-  mean = (float)(sum / Bg);
+  const double md = sum / Bg;
+  mean = (float)md;
   const float mean2 = (float)(sumsq / Bg);
-  const float var = fmaxf(0.f, mean2 - mean * mean);
+  float var = fmaxf(0.f, mean2 - mean * mean);  // flax's form, on fp32 moments
+  // That difference is off by ulp(mean2) / var of itself, 2^-24 mean2 / var.
+  // From mean2 / var = 256 on (a column that varies by under 6% of its level:
+  // a batch of two or three rows, a near-constant condition) that is 1.5e-5
+  // and more, past the 1e-5 every gradient is held to: 6e-4 for a column at
+  // 0.38 whose two rows differ by 0.01 reached the gradient at 2.5e-4 of scale
+  // (test_train_gradient_per_parameter[small-2-86]).  There the difference of
+  // the fp64 moments, rounded once, takes its place.  Better-conditioned
+  // columns keep the fp32 form and with it the bits they always had.
+  if (var * 256.f < mean2) var = fmaxf(0.f, (float)(sumsq / Bg - md * md));
   rstd = 1.0f / sqrtf(var + kBnEps);
   if (update) {
     nat_bn[k] = kBnMomentum * nat_bn[k] + (1.0f - kBnMomentum) * mean;
