@@ -218,6 +218,15 @@ int zf_flow_log_prob_segment(zf_flow_t* h, int op_begin, int op_end, const float
  * `workspace` for N rows -> nll_sum[0] (= sum log_prob; NLL = -nll_sum/N). */
 int zf_flow_nll_reduce(const void* workspace, int64_t N, double* nll_sum, void* stream);
 
+/* Launches of the split-MFMA kernels this handle has made, by form: the
+ * streaming form, the resident form with its generic frame, the resident form
+ * with the frame specialised for D = 4, C = 0, affine ShiftBounds and a Normal
+ * latent.  -1 for a NULL handle or an unknown form. */
+#define ZF_FORM_STREAMING 0
+#define ZF_FORM_RESIDENT 1
+#define ZF_FORM_RESIDENT_FRAME 2
+int64_t zf_flow_launch_count(const zf_flow_t* h, int form);
+
 /* Replaces Chain.__call__ (bijectors.py:103-111) over the op range
  * [op_begin, op_end): x (N,D) -> y (N,D), log_det (N,).  If log_det_in is not
  * NULL its values seed the accumulator (chained segments, train mode). */

@@ -43,6 +43,9 @@ ZF_KERNEL_FP32 = 0
 ZF_KERNEL_BF16X3 = 1
 ZF_KERNEL_F16X2 = 2
 ZF_KERNEL_LAYERED = 3
+ZF_FORM_STREAMING = 0
+ZF_FORM_RESIDENT = 1
+ZF_FORM_RESIDENT_FRAME = 2
 
 
 class ZfOpDesc(C.Structure):
@@ -129,6 +132,7 @@ SIGNATURES = {
     "zf_flow_log_prob": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "zf_flow_log_prob_segment": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "zf_flow_nll_reduce": (_int, [_vp, _i64, _vp, _vp]),
+    "zf_flow_launch_count": (_i64, [_vp, _int]),
     "zf_flow_forward": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "zf_flow_inverse": (_int, [_vp, _int, _int, _vp, _vp, _vp, _i64, _vp]),
     "zf_flow_sample": (_int, [_vp, _u64, _vp, _vp, _i64, _vp]),

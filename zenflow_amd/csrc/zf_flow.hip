@@ -403,6 +403,8 @@ struct zf_flow {
   int ncu = 0;
   float* d_res_state = nullptr;
   long long res_floats = 0;
+  // launches of the split-MFMA kernels by form (zf_flow_launch_count)
+  int64_t n_launch[3] = {0, 0, 0};
   zf::LayeredFlow* lay = nullptr;  // layered eval path (a hidden width > 256), or null
 };
 
@@ -753,6 +755,16 @@ int launch_flow(zf_flow* h, int op_begin, int op_end, const float* x, const floa
     a.seed = seed;
     a.gen = gen;
     a.stream = (hipStream_t)stream;
+    // what the resident form's specialised frame asks of the flow (x3_resident_fits)
+    a.latent = h->host.latent;
+    a.sb_affine = true;
+    for (int i = op_begin; i < op_end; ++i) {
+      if (h->desc.ops[i].kind != ZF_OP_SHIFT_BOUNDS) continue;
+      for (int j = 0; j < h->host.D; ++j) {
+        const int mode = (int)h->packed[(size_t)h->host.ops[i].sb + 8 * j];
+        if (mode != ZF_SB_NONE && mode != ZF_SB_BOTH) a.sb_affine = false;
+      }
+    }
     // the resident form: forced (ZF_X3_RESIDENT=1) or from kX3ResidentAutoRows rows on
     if (h->x3_res_mode != 0 && (h->x3_res_mode == 1 || N >= kX3ResidentAutoRows) &&
         x3_resident_fits(h->desc, a, INV, h->ncu)) {
@@ -770,7 +782,9 @@ int launch_flow(zf_flow* h, int op_begin, int op_end, const float* x, const floa
       }
       if (need <= h->res_floats) a.res_state = h->d_res_state;
     }
-    return launch_flow_x3(a, INV);
+    const int rc = launch_flow_x3(a, INV);
+    if (rc == ZF_OK) ++h->n_launch[a.res_state == nullptr ? 0 : a.res_frame ? 2 : 1];
+    return rc;
   }
   const int64_t grid = (N + kBlockRows - 1) / kBlockRows;
   if (grid > 0x7fffffffLL) return einval("N too large");
@@ -815,6 +829,11 @@ int zf_flow_log_prob_segment(zf_flow_t* h, int op_begin, int op_end, const float
   if (rc) return rc;
   if (nll_sum) return zf_flow_nll_reduce(workspace, N, nll_sum, stream);
   return ZF_OK;
+}
+
+int64_t zf_flow_launch_count(const zf_flow_t* h, int form) {
+  if (!h || form < ZF_FORM_STREAMING || form > ZF_FORM_RESIDENT_FRAME) return -1;
+  return h->n_launch[form];
 }
 
 int zf_flow_nll_reduce(const void* workspace, int64_t N, double* nll_sum, void* stream) {

@@ -384,6 +384,13 @@ struct X3Launch {
   // largest coupling span
   float* res_state = nullptr;
   int res_blocks = 0, res_slots = 0, res_span = 0;
+  // the resident form's specialised frame (D = 4, C = 0, affine ShiftBounds,
+  // Normal latent, no ld_in): what the caller knows of the flow (sb_affine:
+  // every ShiftBounds row of the op range has mode NONE or BOTH), and
+  // x3_resident_fits' decision
+  bool sb_affine = false;
+  int latent = 0;
+  bool res_frame = false;
   hipStream_t stream;
 };
 int launch_flow_x3(const X3Launch& a, bool inverse);

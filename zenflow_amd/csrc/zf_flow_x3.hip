@@ -115,12 +115,29 @@ bool x3_resident_fits(const zf_flow_desc& desc, X3Launch& a, bool inverse, int n
   const long long nslots = (a.N + 127) / 128;
   const long long slots = (nslots + ncu - 1) / ncu;
   if (slots > (1 << 20)) return false;
-  if (x3_res_lds_bytes((size_t)span, a.par_bytes, a.D + a.C, 4 * slots) > 160 * 1024) return false;
+  if (x3_res_lds_bytes((size_t)span, a.par_bytes, a.D + a.C, 4 * slots, false) > 160 * 1024) return false;
   // instantiated: K = 16 with two transformed dims, forward and inverse
   // (zf_flow_x3_k16_res.hip).  One transformed dim (cfg4's shape) fits the
   // budget too but did not beat the streaming form by the A/B margin
   // (profiles/resident_ab.txt), and K = 8 / 32 were not measured.
   if (a.K != 16 || dt != 2) return false;
+  // The specialised frame (flow_kernel_x3r FR): the flagship shape — D = 4,
+  // C = 0, affine ShiftBounds rows only, a Normal latent, no log_det_in —
+  // with at most one ShiftBounds in each run of ops between two couplings
+  // (the frame keeps one set of its constants before and one behind the
+  // pass's coupling).  Everything else keeps the generic frame.
+#ifndef ZF_X3R_FRAME
+#define ZF_X3R_FRAME 1  // tuning: 0 = always the generic frame
+#endif
+  a.res_frame = ZF_X3R_FRAME && a.D == 4 && a.C == 0 && a.sb_affine && a.latent == ZF_LATENT_NORMAL &&
+                a.ld_in == nullptr;
+  for (int i = a.op_begin, run = 0; i < a.op_end && a.res_frame; ++i) {
+    const int kind = desc.ops[i].kind;
+    run = kind == ZF_OP_NSC ? 0 : run + (kind == ZF_OP_SHIFT_BOUNDS ? 1 : 0);
+    if (run > 1) a.res_frame = false;
+  }
+  // the frame's ShiftBounds constants take 128 B of LDS more: a call that only fits without them keeps the generic frame
+  if (x3_res_lds_bytes((size_t)span, a.par_bytes, a.D + a.C, 4 * slots, true) > 160 * 1024) a.res_frame = false;
   a.res_blocks = ncu;
   a.res_slots = (int)slots;
   a.res_span = (int)span;

@@ -1,7 +1,9 @@
 // Resident form of the split-MFMA fused flow kernel (flow_kernel_x3r,
 // zf_flow_x3_kernel.h), K = 16 knots: swish couplings with two transformed
 // dims, forward and inverse / sample — the shapes that measured faster than
-// the streaming form (profiles/resident_ab.txt).  Every other shape stays on
+// the streaming form (profiles/resident_ab.txt), each with the generic frame
+// and with the frame specialised for D = 4, C = 0, affine ShiftBounds and a
+// Normal latent (profiles/resident_frame_ab.txt).  Every other shape stays on
 // the streaming form (x3_resident_fits).
 #include "zf_flow_x3_kernel.h"
 

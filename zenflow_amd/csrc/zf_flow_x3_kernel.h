@@ -1875,9 +1875,11 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
 // every output has the streaming form's bits.
 constexpr int kX3ResWaves = 12;  // three waves per SIMD, as the streaming form's three blocks per CU
 
-// LDS: resident span | one small-parameter region | [12][2][DS + 1][32] state | one fp64 sum per tile
-inline size_t x3_res_lds_bytes(size_t span, int par_bytes, int DS, long long tiles_per_block) {
-  return span + (size_t)par_bytes + (size_t)kX3ResWaves * 2 * (DS + 1) * 32 * 4 + (size_t)tiles_per_block * 8;
+// LDS: resident span | one small-parameter region | [12][2][DS + 1][32] state | one fp64 sum per tile |
+// the specialised frame only: the ShiftBounds constants of the pass ([2][4] x 16 B)
+inline size_t x3_res_lds_bytes(size_t span, int par_bytes, int DS, long long tiles_per_block, bool frame) {
+  return span + (size_t)par_bytes + (size_t)kX3ResWaves * 2 * (DS + 1) * 32 * 4 + (size_t)tiles_per_block * 8 +
+         (frame ? 128 : 0);
 }
 
 // DMA one tile's state (scratch: x [D][32], then the log-det [32]) into a
@@ -1893,7 +1895,133 @@ __device__ __forceinline__ void x3r_fetch(const float* __restrict__ st, float* b
                                      (__attribute__((address_space(3))) void*)(buf + DS * 32), 4, 0, 0);
 }
 
-template <int K, bool ONE, bool INV>
+// ---- the specialised frame (FR) of the resident form: D = 4, C = 0, every
+// ShiftBounds row affine (modes NONE / BOTH), a Normal latent, no log_det_in
+// (x3_resident_fits).  The per-row arithmetic is the generic frame's; what
+// changes is who does it and where its constants come from.
+
+// A pass's invariants in one int: the rotation (0..3) the ShiftBounds before
+// the NSC sees, the one behind it sees, the NSC sees, and the one at the
+// pass's end; whether either ShiftBounds exists; the NSC's op index.
+struct X3rPass {
+  static __device__ __forceinline__ int pack(int rot_sb_before, int rot_sb_after, int rot_nsc, int rot_end,
+                                             bool sb_before, bool sb_after, int nsc_op) {
+    return rot_sb_before | (rot_sb_after << 2) | (rot_nsc << 4) | (rot_end << 6) | (sb_before ? 1 << 8 : 0) |
+           (sb_after ? 1 << 9 : 0) | (nsc_op << 10);
+  }
+  static __device__ __forceinline__ int rot_sb_before(int p) { return p & 3; }
+  static __device__ __forceinline__ int rot_sb_after(int p) { return (p >> 2) & 3; }
+  static __device__ __forceinline__ int rot_nsc(int p) { return (p >> 4) & 3; }
+  static __device__ __forceinline__ int rot_end(int p) { return (p >> 6) & 3; }
+  static __device__ __forceinline__ bool has_sb_before(int p) { return (p >> 8) & 1; }
+  static __device__ __forceinline__ bool has_sb_after(int p) { return (p >> 9) & 1; }
+  static __device__ __forceinline__ int nsc(int p) { return p >> 10; }
+};
+
+// One ShiftBounds dim as the frame keeps it in LDS for a pass: forward
+// {subtrahend, mul, clip flag, the op's summed log-det}, inverse {hi, lo, two-sided flag, 0}.
+template <bool INV>
+__device__ __forceinline__ floatx4 x3r_sb_consts(const float* __restrict__ sb, int i) {
+  const float* r = sb + 8 * i;
+  const bool both = (int)r[0] == ZF_SB_BOTH;
+  floatx4 k;
+  if (!INV) {
+    float ldsb = 0.f;  // shift_bounds_op's sum, in its dimension order
+    for (int j = 0; j < 4; ++j) ldsb = ldsb + sb[8 * j + 6];
+    k[0] = both ? r[1] : r[3];
+    k[1] = r[5];
+    k[2] = both ? 0.f : 1.f;
+    k[3] = ldsb;
+  } else {
+    k[0] = both ? r[2] : r[4];
+    k[1] = both ? r[1] : r[3];
+    k[2] = both ? 1.f : 0.f;
+    k[3] = 0.f;
+  }
+  return k;
+}
+
+// ShiftBounds of an all-affine op on a D = 4 state: each lane half transforms
+// its own two dims (hh, hh + 2); sb_forward_elem's / sb_inverse_elem's
+// expressions for the modes NONE and BOTH.  The inverse's two products and
+// their sum are written out as the one multiply and one fma the compiler
+// contracts sb_inverse_elem's expressions to in every other kernel — which
+// product is rounded on its own differs between the two modes: BOTH
+// fma(1 - z, a, z * b), NONE fma(z, xmax, (1 - z) * xmin) — so that the
+// result does not hang on how this copy happens to be contracted
+// (tests/test_gpu_flow_resident_frame.py, the two-sided flows).
+template <bool INV>
+__device__ __forceinline__ void x3r_shift_bounds(const floatx4* kc, float* xs, int s, int hh, int rot, float& ld) {
+  float ldsb = 0.f;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int i = hh + 2 * e;
+    const floatx4 k = kc[i];
+    float* px = xs + ((i + rot) & 3) * 32 + s;
+    const float v = *px;
+    if (!INV) {
+      const float zr = (v - k[0]) * k[1];
+      *px = (k[2] == 0.f || zr != zr) ? zr : fminf(fmaxf(zr, 0.f), 1.f);
+      ldsb = k[3];
+    } else {
+      const float w = 1.f - v;
+      const float two_sided = __builtin_fmaf(w, k[1], v * k[0]);
+      const float unbounded = __builtin_fmaf(v, k[0], w * k[1]);
+      *px = k[2] != 0.f ? two_sided : unbounded;
+    }
+  }
+  if (!INV) ld = ld + ldsb;
+  wave_lds_sync();
+}
+
+// lane i < m <- lane i + m of a double, without LDS: the moves lane 0's
+// addition tree of the xor butterfly needs (m = 16: v_permlane16_swap; 8, 4,
+// 2, 1: DPP row rotate / row shift / quad permutes).
+template <int M>
+__device__ __forceinline__ double x3r_from_above(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  if constexpr (M == 16) {
+    lo = __builtin_amdgcn_permlane16_swap(lo, lo, false, false)[1];
+    hi = __builtin_amdgcn_permlane16_swap(hi, hi, false, false)[1];
+  } else {
+    constexpr int ctrl = M == 8 ? 0x128 : M == 4 ? 0x104 : M == 2 ? 0x4E : 0xB1;
+    lo = __builtin_amdgcn_update_dpp(lo, lo, ctrl, 0xF, 0xF, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xF, 0xF, false);
+  }
+  return __hiloint2double(hi, lo);
+}
+
+// flow_lp_rows for the Normal latent on a D = 4 state: each half computes the
+// terms of its own dims, the lower half collects the upper half's by
+// v_permlane32_swap and sums all four in flow_lp_rows' order; the fp64 row
+// sum is valid on lane 0 only (the pairs (i, i + m), m = 32 .. 1, of the xor
+// butterfly; m = 32 adds the upper half's zeros).
+__device__ __forceinline__ double x3r_lp_rows(float c0, float c1, const float* xs, int s, int hh, int rot, bool valid,
+                                              float ld, float* __restrict__ lp_tile, bool want_sum) {
+  const float ta = latent_logpdf(ZF_LATENT_NORMAL, c0, c1, 0.f, xs[((hh + rot) & 3) * 32 + s]);
+  const float tb = latent_logpdf(ZF_LATENT_NORMAL, c0, c1, 0.f, xs[((hh + 2 + rot) & 3) * 32 + s]);
+  const float oa = x3_halves(ta).hi, ob = x3_halves(tb).hi;  // lower half: dims 1 and 3
+  float lat = 0.f;
+  lat = lat + ta;
+  lat = lat + oa;
+  lat = lat + tb;
+  lat = lat + ob;
+  const float lp = nan_to_num_lp(lat + ld);
+  if (valid && hh == 0) lp_tile[s] = lp;
+  double v = 0.0;
+  if (want_sum) {
+    v = (valid && hh == 0) ? (double)lp : 0.0;
+    v = v + 0.0;
+    v += x3r_from_above<16>(v);
+    v += x3r_from_above<8>(v);
+    v += x3r_from_above<4>(v);
+    v += x3r_from_above<2>(v);
+    v += x3r_from_above<1>(v);
+  }
+  return v;
+}
+
+template <int K, bool ONE, bool INV, bool FR>
 __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
     const DevFlow* __restrict__ F, const float* __restrict__ blob, const char* __restrict__ x3,
     const float* __restrict__ xin, const float* __restrict__ cin, float* __restrict__ y_out,
@@ -1902,8 +2030,8 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
     float* __restrict__ state, int slots_per_block, int span_bytes) {
   constexpr int NT = 2, T = 4, NW = kX3ResWaves;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int D = F->D;
-  const int C = F->C;
+  const int D = FR ? 4 : F->D;
+  const int C = FR ? 0 : F->C;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int s = lane & 31;
@@ -1932,6 +2060,8 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
   const int nq = op_end - op_begin;
   int rot0 = 0;  // the roll rotation at the start of the pass (the same for every row)
   bool first = true;
+  // FR: the ShiftBounds constants of the pass ([0..3]: the op before the NSC, [4..7]: the one behind it)
+  floatx4* sbk = reinterpret_cast<floatx4*>(s_part + 4 * slots_per_block);
   for (int q = 0; q < nq;) {
     // this pass: the ops up to and including the next NSC; the last pass takes the ops behind it too
     int nsc = -1, seg_end = nq;
@@ -1945,6 +2075,34 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
         }
       }
     const bool last = seg_end == nq;
+    // FR: the pass's invariants — the NSC, at most one ShiftBounds on either
+    // side of it (x3_resident_fits) and the rotation each of them sees —
+    // packed into one scalar (X3rPass) and unpacked per tile, so that a pass
+    // holds one SGPR for them across the coupling body
+    int fr_pack = 0, fr_sba = -1, fr_sbb = -1;
+    if constexpr (FR) {
+      int fr_nsc = 0, fr_rota = 0, fr_rotb = 0, fr_rotn = 0;
+      int rot = rot0;
+      for (int r = q; r < seg_end; ++r) {
+        const int oi = INV ? (op_end - 1 - r) : (op_begin + r);
+        const int kind = F->ops[oi].kind;
+        if (kind == ZF_OP_ROLL) {
+          rot = (INV ? rot + F->ops[oi].shift : rot - F->ops[oi].shift) & 3;
+        } else if (kind == ZF_OP_SHIFT_BOUNDS) {
+          if (r < nsc) {
+            fr_sba = oi;
+            fr_rota = rot;
+          } else {
+            fr_sbb = oi;
+            fr_rotb = rot;
+          }
+        } else {
+          fr_nsc = oi;
+          fr_rotn = rot;
+        }
+      }
+      fr_pack = X3rPass::pack(fr_rota, fr_rotb, fr_rotn, rot, fr_sba >= 0, fr_sbb >= 0, fr_nsc);
+    }
     // every wave of every block passes these two barriers once per pass, whatever its tile list
     __syncthreads();  // all waves are done with the previous coupling's weights
     if (nsc >= 0 && nt > 0) {
@@ -1953,14 +2111,30 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
       x3_dma(x3 + fo.x3, lds, pieces, wave, lane, NW);
       x3_dma(reinterpret_cast<const char*>(blob + fo.bn), par_lds, fo.x3_par_pieces, wave, lane, NW);
     }
+    if constexpr (FR) {
+      int lh = lane;  // an opaque copy: the pass head's per-lane addresses are formed here, not kept
+      asm volatile("" : "+v"(lh));
+      if (wave == 0 && lh < 8) {
+        const int oi = lh < 4 ? fr_sba : fr_sbb;
+        if (oi >= 0) sbk[lh] = x3r_sb_consts<INV>(blob + F->ops[oi].sb, lh & 3);
+      }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // the span and the parameters are complete
 
     int cur = 0;
     if (!first && wave < nt) x3r_fetch(state + (tile0 + wave) * ST, xs0, D, DS, lane);
+    float lat_c0 = 0.f, lat_c1 = 1.f;
+    if (FR && last && lp_out != nullptr) {
+      lat_c0 = F->lat_c0;
+      lat_c1 = F->lat_c1;
+    }
     for (int t = wave; t < nt; t += NW) {
       float* xs = xs0 + cur * SB;
       const long long tile = tile0 + t;
+      // rows of this tile that exist (FR: the row index stays a 32-bit offset from the tile's base)
+      const long long nleft = N - tile * kTile;
+      const int nrows = nleft < kTile ? (int)nleft : kTile;
       // The tile's load and store code takes its lane index through an
       // opaque copy, so its per-lane addresses are formed here and not kept
       // in registers across the coupling as invariants of the tile loop.
@@ -1969,9 +2143,21 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
       {
         const int s1 = ln & 31, h1 = ln >> 5;
         const long long row1 = tile * kTile + s1;
-        const bool valid1 = row1 < N;
+        const bool valid1 = FR ? s1 < nrows : row1 < N;
         if (first) {
-          load_state(xs, xin, row1, valid1, D, s1, h1, F, seed, INV ? gen : 0);
+          if constexpr (FR) {
+            // load_state with the Normal latent; the row's offset from the tile's base is 32-bit
+            const float lat_c3 = F->lat_c3;
+            const float* xt = xin + tile * (kTile * 4);
+#pragma unroll
+            for (int d = h1; d < 4; d += 2) {
+              float v = 0.f;
+              if (valid1) v = (INV && gen) ? latent_draw(ZF_LATENT_NORMAL, lat_c3, seed, row1, d) : xt[s1 * 4 + d];
+              xs[d * 32 + s1] = v;
+            }
+          } else {
+            load_state(xs, xin, row1, valid1, D, s1, h1, F, seed, INV ? gen : 0);
+          }
         } else if (t == wave) {
           // later tiles' state was waited for before the previous tile's stores (below)
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1983,29 +2169,49 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
       float ld;
       if (first) {
         const long long row1 = tile * kTile + (ln & 31);
-        ld = (ld_in != nullptr && row1 < N) ? ld_in[row1] : 0.f;
+        ld = (!FR && ld_in != nullptr && row1 < N) ? ld_in[row1] : 0.f;
       } else {
         ld = xs[DS * 32 + (ln & 31)];
         if (t + NW < nt) x3r_fetch(state + (tile + NW) * ST, xs0 + (cur ^ 1) * SB, D, DS, ln);
       }
       int rot = rot0;
-      for (int r = q; r < seg_end; ++r) {
-        const DevOp& op = F->ops[INV ? (op_end - 1 - r) : (op_begin + r)];
-        const X3Sc opc = x3_scalars<INV>(op);
-        if (opc.kind == ZF_OP_ROLL) {
-          rot = pmod(INV ? rot + opc.shift : rot - opc.shift, D);
-        } else if (opc.kind == ZF_OP_SHIFT_BOUNDS) {
-          shift_bounds_op<INV>(blob + opc.sb, xs, s, hh, rot, D, ld);
-        } else {
-          // an opaque zero keeps the span's and the parameters' per-lane LDS
-          // addresses inside the coupling (hoisted out of the tile loop as
-          // loop invariants they cost 44 spilled VGPRs)
+      if constexpr (FR) {
+        int fp = fr_pack;
+        asm volatile("" : "+s"(fp));
+        if (X3rPass::has_sb_before(fp)) x3r_shift_bounds<INV>(sbk, xs, s, hh, X3rPass::rot_sb_before(fp), ld);
+        {
+          const DevOp& op = F->ops[X3rPass::nsc(fp)];
+          const X3Sc opc = x3_scalars<INV>(op);
           int zoff = 0;
           asm volatile("" : "+s"(zoff));
           pipe.cur = lds + zoff;
           pipe.g = 0;
           x3_nsc<NT, K, T, false, ONE, INV, false, 0, true>(
-              op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, rot, D, s, hh, lane, ld, tr);
+              op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, X3rPass::rot_nsc(fp), 4, s, hh, lane, ld,
+              tr);
+        }
+        asm volatile("" : "+s"(fp));
+        if (X3rPass::has_sb_after(fp)) x3r_shift_bounds<INV>(sbk + 4, xs, s, hh, X3rPass::rot_sb_after(fp), ld);
+        rot = X3rPass::rot_end(fp);
+      } else {
+        for (int r = q; r < seg_end; ++r) {
+          const DevOp& op = F->ops[INV ? (op_end - 1 - r) : (op_begin + r)];
+          const X3Sc opc = x3_scalars<INV>(op);
+          if (opc.kind == ZF_OP_ROLL) {
+            rot = pmod(INV ? rot + opc.shift : rot - opc.shift, D);
+          } else if (opc.kind == ZF_OP_SHIFT_BOUNDS) {
+            shift_bounds_op<INV>(blob + opc.sb, xs, s, hh, rot, D, ld);
+          } else {
+            // an opaque zero keeps the span's and the parameters' per-lane LDS
+            // addresses inside the coupling (hoisted out of the tile loop as
+            // loop invariants they cost 44 spilled VGPRs)
+            int zoff = 0;
+            asm volatile("" : "+s"(zoff));
+            pipe.cur = lds + zoff;
+            pipe.g = 0;
+            x3_nsc<NT, K, T, false, ONE, INV, false, 0, true>(
+                op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, rot, D, s, hh, lane, ld, tr);
+          }
         }
       }
       // the next tile's state has landed (issued a whole tile ago), so the
@@ -2014,12 +2220,29 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
       asm volatile("" : "+v"(ln));
       const int s2 = ln & 31, h2 = ln >> 5;
       const long long row = tile * kTile + s2;
-      const bool valid = row < N;
+      const bool valid = FR ? s2 < nrows : row < N;
       if (!last) {
         float* st = state + tile * ST;
+        if constexpr (FR) {
+#pragma unroll
+          for (int d = h2; d < 4; d += 2) st[d * 32 + s2] = xs[d * 32 + s2];
+        } else {
 #pragma nounroll
-        for (int d = h2; d < D; d += 2) st[d * 32 + s2] = xs[d * 32 + s2];
+          for (int d = h2; d < D; d += 2) st[d * 32 + s2] = xs[d * 32 + s2];
+        }
         if (h2 == 0) st[D * 32 + s2] = ld;
+      } else if constexpr (FR) {
+        if (lp_out != nullptr) {
+          const double v = x3r_lp_rows(lat_c0, lat_c1, xs, s2, h2, rot, valid, ld, lp_out + tile * kTile,
+                                       block_partial != nullptr);
+          if (block_partial != nullptr && ln == 0) s_part[t] = v;
+        }
+        if (y_out != nullptr && valid) {
+          float* yt = y_out + tile * (kTile * 4);
+#pragma unroll
+          for (int j = h2; j < 4; j += 2) yt[s2 * 4 + j] = xs[((j + rot) & 3) * 32 + s2];
+        }
+        if (ld_out != nullptr && valid && h2 == 0) (ld_out + tile * kTile)[s2] = ld;
       } else {
         if (lp_out != nullptr) {
           const double v = flow_lp_rows(F, xs, s2, h2, rot, D, row, valid, ld, lp_out, block_partial != nullptr);
@@ -2051,16 +2274,25 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
 
 template <int K, bool ONE>
 int launch_x3r(const X3Launch& a, bool inverse) {
-  const size_t lds = x3_res_lds_bytes((size_t)a.res_span, a.par_bytes, a.D + a.C, 4ll * a.res_slots);
+  const size_t lds = x3_res_lds_bytes((size_t)a.res_span, a.par_bytes, a.D + a.C, 4ll * a.res_slots, !ONE && a.res_frame);
   if (lds > 160 * 1024 || a.res_state == nullptr) return enotsup("resident split-MFMA kernel: shape");
-  if (inverse)
-    hipLaunchKernelGGL((flow_kernel_x3r<K, ONE, true>), dim3((unsigned)a.res_blocks), dim3(kX3ResWaves * 64), lds,
-                       a.stream, a.desc, a.blob, (const char*)a.x3, a.x, a.c, a.y, a.ld_in, a.ld_out, a.lp, a.part,
-                       a.op_begin, a.op_end, a.N, a.seed, a.gen, a.res_state, a.res_slots, a.res_span);
-  else
-    hipLaunchKernelGGL((flow_kernel_x3r<K, ONE, false>), dim3((unsigned)a.res_blocks), dim3(kX3ResWaves * 64), lds,
-                       a.stream, a.desc, a.blob, (const char*)a.x3, a.x, a.c, a.y, a.ld_in, a.ld_out, a.lp, a.part,
-                       a.op_begin, a.op_end, a.N, a.seed, a.gen, a.res_state, a.res_slots, a.res_span);
+#define ZF_X3R_LAUNCH(INVV, FRV)                                                                                     \
+  hipLaunchKernelGGL((flow_kernel_x3r<K, ONE, INVV, FRV>), dim3((unsigned)a.res_blocks), dim3(kX3ResWaves * 64), lds, \
+                     a.stream, a.desc, a.blob, (const char*)a.x3, a.x, a.c, a.y, a.ld_in, a.ld_out, a.lp, a.part,    \
+                     a.op_begin, a.op_end, a.N, a.seed, a.gen, a.res_state, a.res_slots, a.res_span)
+  if constexpr (!ONE) {
+    if (a.res_frame) {
+      if (inverse) ZF_X3R_LAUNCH(true, true);
+      else ZF_X3R_LAUNCH(false, true);
+    } else {
+      if (inverse) ZF_X3R_LAUNCH(true, false);
+      else ZF_X3R_LAUNCH(false, false);
+    }
+  } else {
+    if (inverse) ZF_X3R_LAUNCH(true, false);
+    else ZF_X3R_LAUNCH(false, false);
+  }
+#undef ZF_X3R_LAUNCH
   ZF_CHECK_LAUNCH("flow_kernel_x3r");
   return ZF_OK;
 }

@@ -147,6 +147,14 @@ class Program:
         v = L.load_library().zf_flow_kernel_variant(ct.c_void_p(self.handle))
         return {L.ZF_KERNEL_F16X2: "f16x2", L.ZF_KERNEL_BF16X3: "bf16x3", L.ZF_KERNEL_LAYERED: "layered"}.get(v, "fp32")
 
+    def launch_count(self, form: str) -> int:
+        """Launches of the split-MFMA kernels this program has made in one form: 'streaming',
+        'resident' (the resident form's generic frame) or 'resident_frame' (its frame specialised
+        for D = 4, C = 0, affine ShiftBounds and a Normal latent; zf_flow_launch_count)."""
+        f = {"streaming": L.ZF_FORM_STREAMING, "resident": L.ZF_FORM_RESIDENT,
+             "resident_frame": L.ZF_FORM_RESIDENT_FRAME}[form]
+        return int(L.load_library().zf_flow_launch_count(ct.c_void_p(self.handle), f))
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h and L._lib is not None:
