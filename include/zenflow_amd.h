@@ -389,6 +389,91 @@ int zf_trainer_get_blob(zf_trainer_t* trainer, float* blob_host);
 int zf_trainer_set_blob(zf_trainer_t* trainer, const float* blob_host);
 
 /* ------------------------------------------------------------------------ */
+/* Optimiser chains — optax.GradientTransformation, which the reference's    */
+/* train() takes (train.py:27, 62, 84-85), restated from optax's published   */
+/* formulas (optax is not a dependency).  count = updates already applied,   */
+/* t = count + 1; u starts as the gradient, the step ends with theta += u.   */
+/* ------------------------------------------------------------------------ */
+
+/* Stage kinds; p[] and flags of zf_optim_stage per kind. */
+#define ZF_OPT_CLIP_BY_GLOBAL_NORM 1   /* optax.clip_by_global_norm: p[0] max_norm */
+#define ZF_OPT_CLIP 2                  /* optax.clip: p[0] max_delta */
+#define ZF_OPT_SCALE_BY_ADAM 3         /* optax.scale_by_adam: p = b1, b2, eps, eps_root; NESTEROV */
+#define ZF_OPT_SCALE_BY_LION 4         /* optax.scale_by_lion: p = b1, b2 */
+#define ZF_OPT_TRACE 5                 /* optax.trace: p[0] decay; NESTEROV */
+#define ZF_OPT_ADD_DECAYED_WEIGHTS 6   /* optax.add_decayed_weights: p[0] weight_decay; MASKED */
+#define ZF_OPT_SCALE 7                 /* optax.scale: p[0] step_size */
+#define ZF_OPT_SCALE_BY_LEARNING_RATE 8 /* optax.scale_by_learning_rate: u <- -lr(count) u; sched */
+#define ZF_OPT_FLAG_NESTEROV 1
+#define ZF_OPT_FLAG_MASKED 2           /* add_decayed_weights only where decay_mask is set */
+#define ZF_OPT_MAX_STAGES 8
+#define ZF_OPT_MAX_SLOTS 4             /* moment arrays: adam 2 (m, v), lion 1, trace 1 */
+
+/* Schedule kinds (optax.schedules); p[] of a segment per kind. */
+#define ZF_SCHED_CONSTANT 0     /* optax.constant_schedule: p[0] value */
+#define ZF_SCHED_LINEAR 1       /* optax.linear_schedule: p = init, end, transition_steps, transition_begin */
+#define ZF_SCHED_COSINE 2       /* optax.cosine_decay_schedule: p = init, decay_steps, alpha, exponent */
+#define ZF_SCHED_EXPONENTIAL 3  /* optax.exponential_decay: p = init, transition_steps, decay_rate,
+                                   transition_begin, staircase (0 / 1), end_value, has_end_value (0 / 1) */
+#define ZF_SCHED_PIECEWISE 4    /* optax.piecewise_constant_schedule: p = init, n, b0, s0, b1, s1, b2, s2:
+                                   init times every scale s_i whose boundary b_i < count */
+#define ZF_SCHED_JOIN 5         /* optax.join_schedules: the top-level kind of n_segments > 1 */
+#define ZF_SCHED_MAX_SEGMENTS 4
+#define ZF_SCHED_PARAMS 8
+
+/* A schedule count -> value, evaluated on the device in double from the
+ * device's own step counter.  n_segments == 1: seg_kind[0] (== kind) on
+ * p[0].  optax.join_schedules: kind ZF_SCHED_JOIN, segment k (the last one
+ * with count >= boundary[k]; boundary[0] = 0) sees count - boundary[k]. */
+typedef struct zf_schedule {
+  int kind;
+  int n_segments;
+  int seg_kind[ZF_SCHED_MAX_SEGMENTS];
+  double boundary[ZF_SCHED_MAX_SEGMENTS];
+  double p[ZF_SCHED_MAX_SEGMENTS][ZF_SCHED_PARAMS];
+} zf_schedule;
+
+typedef struct zf_optim_stage {
+  int kind;   /* ZF_OPT_* */
+  int flags;  /* ZF_OPT_FLAG_* */
+  float p[4];
+  zf_schedule sched; /* ZF_OPT_SCALE_BY_LEARNING_RATE only */
+} zf_optim_stage;
+
+/* optax.chain: the stages in order. */
+typedef struct zf_optim_chain {
+  int n_stages; /* 1 .. ZF_OPT_MAX_STAGES */
+  int _pad;
+  zf_optim_stage stages[ZF_OPT_MAX_STAGES];
+} zf_optim_chain;
+
+/* Replace the trainer's optimiser (zf_optim_desc's (n)adamw) by a chain;
+ * zf_trainer_step* then run it on the device, inside the captured step graph
+ * too.  decay_mask: one byte per blob entry (optax's `mask` of
+ * add_decayed_weights, lowered to the blob) or NULL (every parameter).
+ * Synchronises, drops the cached step graphs, allocates one zeroed blob-sized
+ * array per moment and resets the count.  ZF_ENOTSUP (the message names the
+ * stage): more than ZF_OPT_MAX_STAGES stages or ZF_OPT_MAX_SLOTS moment
+ * arrays, more than one clip_by_global_norm, or one that follows a stage
+ * that changes u (the norm is that of the raw gradient). */
+int zf_trainer_set_optim_chain(zf_trainer_t* trainer, const zf_optim_chain* chain,
+                               const unsigned char* decay_mask);
+
+/* optax's optimiser state, for checkpoints: moment array `slot` (blob
+ * layout, blob_floats host floats) in chain order — scale_by_adam: mu, nu;
+ * scale_by_lion: mu; trace: trace.  Without a chain: 0 = m, 1 = v of the
+ * (n)adamw update. */
+int zf_trainer_get_opt_slot(zf_trainer_t* trainer, int slot, float* host_floats);
+int zf_trainer_set_opt_slot(zf_trainer_t* trainer, int slot, const float* host_floats);
+
+/* count (optax's ScaleByAdamState.count and its like), and what the last
+ * step used: the learning rate and the gradient's global norm (NaN without
+ * clip_by_global_norm).  Any pointer may be NULL.  set_opt_count restores the
+ * counter (and the bias corrections that follow from it). */
+int zf_trainer_get_opt_scalars(zf_trainer_t* trainer, int64_t* count, double* learning_rate, double* grad_norm);
+int zf_trainer_set_opt_count(zf_trainer_t* trainer, int64_t count);
+
+/* ------------------------------------------------------------------------ */
 /* RCCL (over xGMI) — the NLL all-reduce of data-parallel log_prob and the  */
 /* trainer's all-gather.                                                      */
 /* ------------------------------------------------------------------------ */

@@ -46,6 +46,26 @@ ZF_KERNEL_LAYERED = 3
 ZF_FORM_STREAMING = 0
 ZF_FORM_RESIDENT = 1
 ZF_FORM_RESIDENT_FRAME = 2
+ZF_OPT_CLIP_BY_GLOBAL_NORM = 1
+ZF_OPT_CLIP = 2
+ZF_OPT_SCALE_BY_ADAM = 3
+ZF_OPT_SCALE_BY_LION = 4
+ZF_OPT_TRACE = 5
+ZF_OPT_ADD_DECAYED_WEIGHTS = 6
+ZF_OPT_SCALE = 7
+ZF_OPT_SCALE_BY_LEARNING_RATE = 8
+ZF_OPT_FLAG_NESTEROV = 1
+ZF_OPT_FLAG_MASKED = 2
+ZF_OPT_MAX_STAGES = 8
+ZF_OPT_MAX_SLOTS = 4
+ZF_SCHED_CONSTANT = 0
+ZF_SCHED_LINEAR = 1
+ZF_SCHED_COSINE = 2
+ZF_SCHED_EXPONENTIAL = 3
+ZF_SCHED_PIECEWISE = 4
+ZF_SCHED_JOIN = 5
+ZF_SCHED_MAX_SEGMENTS = 4
+ZF_SCHED_PARAMS = 8
 
 
 class ZfOpDesc(C.Structure):
@@ -67,6 +87,20 @@ class ZfOpDesc(C.Structure):
 class ZfOptimDesc(C.Structure):
     _fields_ = [("learning_rate", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("nesterov", C.c_int)]
+
+
+class ZfSchedule(C.Structure):
+    _fields_ = [("kind", C.c_int), ("n_segments", C.c_int), ("seg_kind", C.c_int * ZF_SCHED_MAX_SEGMENTS),
+                ("boundary", C.c_double * ZF_SCHED_MAX_SEGMENTS),
+                ("p", (C.c_double * ZF_SCHED_PARAMS) * ZF_SCHED_MAX_SEGMENTS)]
+
+
+class ZfOptimStage(C.Structure):
+    _fields_ = [("kind", C.c_int), ("flags", C.c_int), ("p", C.c_float * 4), ("sched", ZfSchedule)]
+
+
+class ZfOptimChain(C.Structure):
+    _fields_ = [("n_stages", C.c_int), ("_pad", C.c_int), ("stages", ZfOptimStage * ZF_OPT_MAX_STAGES)]
 
 
 # zf_allgather_fn(ctx, send, recv, bytes, stream) and zf_comm_desc
@@ -148,6 +182,11 @@ SIGNATURES = {
     "zf_trainer_log_prob_vjp": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "zf_trainer_get_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_blob": (_int, [_vp, _vp]),
+    "zf_trainer_set_optim_chain": (_int, [_vp, _vp, _vp]),
+    "zf_trainer_get_opt_slot": (_int, [_vp, _int, _vp]),
+    "zf_trainer_set_opt_slot": (_int, [_vp, _int, _vp]),
+    "zf_trainer_get_opt_scalars": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "zf_trainer_set_opt_count": (_int, [_vp, _i64]),
     "zf_latent_sample": (_int, [_int, _dbl, _u64, _vp, _i64, _int, _vp]),
     "zf_flow_set_bn_stats": (_int, [_vp, _int, _vp, _vp]),
     "zf_flow_set_sb_stats": (_int, [_vp, _int, _vp, _vp]),

@@ -18,6 +18,7 @@
 // zf_flow_plan on the device.
 #include "zf_act.h"
 #include "zf_internal.h"
+#include "zf_optim.h"
 #include "zf_spline.h"
 
 #include <algorithm>
@@ -2128,6 +2129,20 @@ struct zf_trainer {
   float* d_state = nullptr;   // [n_ops + 1][bmax][D] states before each op
   float* d_c = nullptr;       // [bmax][C] conditioning inputs of the batch
   float* d_bc = nullptr;      // optimiser step count + bias corrections (step_kernel)
+  // optimiser chain (zf_trainer_set_optim_chain); off: the (n)adamw of `opt`
+  bool chain_on = false;
+  zf::ChainArgs cargs{};
+  int chain_form = 0;         // kForm*
+  int n_slots = 0;
+  float max_norm = 0.f;       // clip_by_global_norm (chain_clip)
+  bool chain_clip = false, chain_lr = false, chain_adam = false;
+  float chain_b1 = 0.f, chain_b2 = 0.f;  // the scale_by_adam stage's, for the bias corrections
+  zf_schedule sched{};
+  std::vector<void*> opt_bufs;  // what the chain allocated (freed when it is replaced)
+  unsigned char* d_dmask = nullptr;
+  double* d_nleaf = nullptr;  // leaves of the gradient's sum of squares
+  int n_nleaf = 0;
+  zf::OptScalars* d_osc = nullptr;
   // zf_trainer_step as one hipGraph per batch size (the body reads only the
   // trainer's own buffers: x and c are copied in before the launch)
   hipStream_t cap = nullptr;
@@ -2311,6 +2326,7 @@ int zf_trainer_destroy(zf_trainer_t* t) {
   for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
   if (t->cap) (void)hipStreamDestroy(t->cap);
   for (float* p : t->bufs) (void)hipFree(p);
+  for (void* p : t->opt_bufs) (void)hipFree(p);
   if (t->d_gath) (void)hipFree(t->d_gath);
   delete t;
   return ZF_OK;
@@ -2617,7 +2633,16 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
   return ZF_OK;
 }
 
+// The chain's step (zf_optim.hip): the gradient is in t->d_grad, its cast did
+// not step (trainer_body with step_in_cast = nullptr).
+int chain_update(zf_trainer_t* t, hipStream_t st) {
+  return optim_chain_step(t->d_nat, t->d_grad, t->d_mask, t->d_dmask, (long long)t->nat_floats, t->cargs,
+                          t->chain_form, t->chain_clip, t->max_norm, t->chain_lr, t->sched, t->chain_adam,
+                          t->chain_b1, t->chain_b2, t->d_osc, t->d_nleaf, t->n_nleaf, st);
+}
+
 int trainer_update(zf_trainer_t* t, hipStream_t st, bool step_done = false) {
+  if (t->chain_on) return chain_update(t, st);
   const zf_optim_desc& o = t->opt;
   if (!step_done) {
     hipLaunchKernelGGL(step_kernel, dim3(1), dim3(1), 0, st, t->d_bc, o.b1, o.b2);
@@ -2775,7 +2800,7 @@ int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out) {
   }
   ZF_TRY_HIP(hipStreamBeginCapture(t->cap, hipStreamCaptureModeThreadLocal));
   bool stepped = false;
-  int rc = trainer_body(t, B, B, 1, t->d_grad, t->cap, &stepped);
+  int rc = trainer_body(t, B, B, 1, t->d_grad, t->cap, t->chain_on ? nullptr : &stepped);
   if (!rc) rc = trainer_update(t, t->cap, stepped);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(t->cap, &g);
@@ -2847,7 +2872,7 @@ int zf_trainer_step_shard(zf_trainer_t* t, const float* x, const float* c, int64
     ZF_TRY_HIP(hipGraphLaunch(exec, st));
   } else {
     bool stepped = false;
-    rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, &stepped);
+    rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped);
     if (!rc) rc = zf::trainer_update(t, st, stepped);
     if (rc) return rc;
   }
@@ -2869,7 +2894,7 @@ int zf_trainer_step_cond_shard(zf_trainer_t* t, const float* x, const float* c, 
   if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
     return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
   bool stepped = false;
-  rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, &stepped, gc);
+  rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped, gc);
   if (!rc) rc = zf::trainer_update(t, st, stepped);
   if (rc) return rc;
   t->t += 1;
@@ -2912,6 +2937,233 @@ int zf_trainer_set_blob(zf_trainer_t* t, const float* blob_host) {
   if (!t || !blob_host) return zf::einval("NULL argument");
   ZF_TRY_HIP(hipDeviceSynchronize());
   ZF_TRY_HIP(hipMemcpy(t->d_nat, blob_host, t->nat_floats * sizeof(float), hipMemcpyHostToDevice));
+  return ZF_OK;
+}
+
+}  // extern "C"
+
+namespace zf {
+namespace {
+
+// enotsup with a formatted message
+int enotsupf(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return enotsup(buf);
+}
+
+const char* stage_name(int kind) {
+  switch (kind) {
+    case ZF_OPT_CLIP_BY_GLOBAL_NORM: return "clip_by_global_norm";
+    case ZF_OPT_CLIP: return "clip";
+    case ZF_OPT_SCALE_BY_ADAM: return "scale_by_adam";
+    case ZF_OPT_SCALE_BY_LION: return "scale_by_lion";
+    case ZF_OPT_TRACE: return "trace";
+    case ZF_OPT_ADD_DECAYED_WEIGHTS: return "add_decayed_weights";
+    case ZF_OPT_SCALE: return "scale";
+    case ZF_OPT_SCALE_BY_LEARNING_RATE: return "scale_by_learning_rate";
+    default: return nullptr;
+  }
+}
+
+int stage_slots(int kind) {
+  return kind == ZF_OPT_SCALE_BY_ADAM ? 2 : (kind == ZF_OPT_SCALE_BY_LION || kind == ZF_OPT_TRACE) ? 1 : 0;
+}
+
+int check_schedule(const zf_schedule& s) {
+  if (s.n_segments < 1 || s.n_segments > ZF_SCHED_MAX_SEGMENTS)
+    return enotsupf("optimiser chain: a schedule of %d joined segments (at most %d)", s.n_segments,
+                   ZF_SCHED_MAX_SEGMENTS);
+  for (int k = 0; k < s.n_segments; ++k) {
+    if (s.seg_kind[k] < ZF_SCHED_CONSTANT || s.seg_kind[k] > ZF_SCHED_PIECEWISE)
+      return einval("optimiser chain: schedule segment %d has unknown kind %d", k, s.seg_kind[k]);
+    if (s.seg_kind[k] == ZF_SCHED_PIECEWISE && (s.p[k][1] < 0 || s.p[k][1] > 3))
+      return enotsupf("optimiser chain: piecewise_constant_schedule with more than 3 boundaries");
+    if (s.seg_kind[k] == ZF_SCHED_COSINE && !(s.p[k][1] > 0))
+      return einval("optimiser chain: cosine_decay_schedule needs decay_steps > 0");
+    if (s.seg_kind[k] == ZF_SCHED_EXPONENTIAL && !(s.p[k][1] > 0))
+      return einval("optimiser chain: exponential_decay needs transition_steps > 0");
+  }
+  return ZF_OK;
+}
+
+void free_chain(zf_trainer_t* t) {
+  for (void* p : t->opt_bufs) (void)hipFree(p);
+  t->opt_bufs.clear();
+  t->d_dmask = nullptr;
+  t->d_nleaf = nullptr;
+  t->d_osc = nullptr;
+  t->n_slots = 0;
+  t->chain_on = false;
+}
+
+int opt_alloc(zf_trainer_t* t, void** p, size_t bytes) {
+  *p = nullptr;
+  ZF_TRY_HIP(hipMalloc(p, bytes ? bytes : 1));
+  t->opt_bufs.push_back(*p);
+  ZF_TRY_HIP(hipMemset(*p, 0, bytes ? bytes : 1));
+  return ZF_OK;
+}
+
+}  // namespace
+}  // namespace zf
+
+extern "C" {
+
+int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, const unsigned char* decay_mask) {
+  if (!t || !chain) return zf::einval("NULL argument");
+  const int S = chain->n_stages;
+  if (S < 1) return zf::einval("optimiser chain: no stage");
+  if (S > ZF_OPT_MAX_STAGES)
+    return zf::enotsupf("optimiser chain: %d stages (at most %d)", S, ZF_OPT_MAX_STAGES);
+  zf::ChainArgs a{};
+  a.n = S;
+  int slots = 0, n_clip = 0, n_adam = 0, n_lr = 0, lr_at = -1, adam_at = -1;
+  bool masked = false;
+  for (int k = 0; k < S; ++k) {
+    const zf_optim_stage& s = chain->stages[k];
+    const char* name = zf::stage_name(s.kind);
+    if (!name) return zf::einval("optimiser chain: stage %d has unknown kind %d", k, s.kind);
+    if (s.kind == ZF_OPT_CLIP_BY_GLOBAL_NORM) {
+      if (++n_clip > 1) return zf::enotsupf("optimiser chain: stage %d: more than one clip_by_global_norm", k);
+      if (k != 0)
+        return zf::enotsupf("optimiser chain: stage %d: clip_by_global_norm after %s (it must come before every "
+                           "stage that changes the update: the norm is the raw gradient's)", k,
+                           zf::stage_name(chain->stages[k - 1].kind));
+    }
+    if (s.kind == ZF_OPT_SCALE_BY_ADAM && ++n_adam > 1)
+      return zf::enotsupf("optimiser chain: stage %d: more than one scale_by_adam", k);
+    if (s.kind == ZF_OPT_SCALE_BY_LEARNING_RATE) {
+      if (++n_lr > 1) return zf::enotsupf("optimiser chain: stage %d: more than one scale_by_learning_rate", k);
+      const int rc = zf::check_schedule(s.sched);
+      if (rc) return rc;
+      lr_at = k;
+    }
+    if (s.kind == ZF_OPT_SCALE_BY_ADAM) adam_at = k;
+    if (s.kind == ZF_OPT_ADD_DECAYED_WEIGHTS && (s.flags & ZF_OPT_FLAG_MASKED)) {
+      if (!decay_mask) return zf::einval("optimiser chain: stage %d: add_decayed_weights is masked but decay_mask is NULL", k);
+      masked = true;
+    }
+    a.st[k].kind = s.kind;
+    a.st[k].flags = s.flags;
+    a.st[k].slot = slots;
+    for (int j = 0; j < 4; ++j) a.st[k].p[j] = s.p[j];
+    slots += zf::stage_slots(s.kind);
+    if (slots > ZF_OPT_MAX_SLOTS)
+      return zf::enotsupf("optimiser chain: stage %d (%s) needs moment array %d (at most %d)", k, name, slots,
+                         ZF_OPT_MAX_SLOTS);
+  }
+  // the forms the aliases build: [clip] body [decay] lr
+  const int first = n_clip;
+  auto kind = [&](int k) { return k < S ? chain->stages[k].kind : 0; };
+  int form = zf::kFormGeneric;
+  if (kind(S - 1) == ZF_OPT_SCALE_BY_LEARNING_RATE) {
+    if (S == first + 1 || (S == first + 2 && kind(first) == ZF_OPT_TRACE)) form = zf::kFormSgd;
+    const bool body_decay = S == first + 3 && kind(first + 1) == ZF_OPT_ADD_DECAYED_WEIGHTS;
+    if ((S == first + 2 || body_decay) && kind(first) == ZF_OPT_SCALE_BY_ADAM) form = zf::kFormAdam;
+    if ((S == first + 2 || body_decay) && kind(first) == ZF_OPT_SCALE_BY_LION) form = zf::kFormLion;
+  }
+  ZF_TRY_HIP(hipStreamSynchronize(t->cap));
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
+  t->graphs.clear();
+  zf::free_chain(t);
+  const size_t need = (size_t)t->nat_floats;
+  int rc = ZF_OK;
+  for (int k = 0; k < slots && !rc; ++k) rc = zf::opt_alloc(t, (void**)&a.slot[k], need * sizeof(float));
+  if (!rc && masked) {
+    rc = zf::opt_alloc(t, (void**)&t->d_dmask, need);
+    if (!rc) {
+      const hipError_t e = hipMemcpy(t->d_dmask, decay_mask, need, hipMemcpyHostToDevice);
+      if (e != hipSuccess) rc = zf::hip_status(e, "zf_trainer_set_optim_chain mask");
+    }
+  }
+  t->n_nleaf = (int)((t->nat_floats + zf::kNormSpan - 1) / zf::kNormSpan);
+  if (!rc) rc = zf::opt_alloc(t, (void**)&t->d_nleaf, (size_t)(t->n_nleaf > 0 ? t->n_nleaf : 1) * sizeof(double));
+  if (!rc) rc = zf::opt_alloc(t, (void**)&t->d_osc, sizeof(zf::OptScalars));
+  if (rc) {
+    zf::free_chain(t);
+    return rc;
+  }
+  t->cargs = a;
+  t->chain_form = form;
+  t->n_slots = slots;
+  t->chain_clip = n_clip > 0;
+  t->max_norm = n_clip ? chain->stages[0].p[0] : 0.f;
+  t->chain_lr = lr_at >= 0;
+  if (lr_at >= 0) t->sched = chain->stages[lr_at].sched;
+  t->chain_adam = adam_at >= 0;
+  t->chain_b1 = adam_at >= 0 ? chain->stages[adam_at].p[0] : 0.f;
+  t->chain_b2 = adam_at >= 0 ? chain->stages[adam_at].p[1] : 0.f;
+  t->t = 0;
+  t->chain_on = true;
+  return ZF_OK;
+}
+
+static int opt_slot_ptr(zf_trainer_t* t, int slot, float** p) {
+  if (!t) return zf::einval("trainer is NULL");
+  const int n = t->chain_on ? t->n_slots : 2;
+  if (slot < 0 || slot >= n) return zf::einval("optimiser slot %d outside [0, %d)", slot, n);
+  *p = t->chain_on ? t->cargs.slot[slot] : (slot == 0 ? t->d_m : t->d_v);
+  return ZF_OK;
+}
+
+int zf_trainer_get_opt_slot(zf_trainer_t* t, int slot, float* host_floats) {
+  float* p = nullptr;
+  const int rc = opt_slot_ptr(t, slot, &p);
+  if (rc) return rc;
+  if (!host_floats) return zf::einval("NULL argument");
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  ZF_TRY_HIP(hipMemcpy(host_floats, p, t->nat_floats * sizeof(float), hipMemcpyDeviceToHost));
+  return ZF_OK;
+}
+
+int zf_trainer_set_opt_slot(zf_trainer_t* t, int slot, const float* host_floats) {
+  float* p = nullptr;
+  const int rc = opt_slot_ptr(t, slot, &p);
+  if (rc) return rc;
+  if (!host_floats) return zf::einval("NULL argument");
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  ZF_TRY_HIP(hipMemcpy(p, host_floats, t->nat_floats * sizeof(float), hipMemcpyHostToDevice));
+  return ZF_OK;
+}
+
+int zf_trainer_get_opt_scalars(zf_trainer_t* t, int64_t* count, double* learning_rate, double* grad_norm) {
+  if (!t) return zf::einval("trainer is NULL");
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  if (t->chain_on) {
+    zf::OptScalars sc;
+    ZF_TRY_HIP(hipMemcpy(&sc, t->d_osc, sizeof(sc), hipMemcpyDeviceToHost));
+    if (count) *count = sc.count;
+    if (learning_rate) *learning_rate = (double)sc.lr;
+    if (grad_norm) *grad_norm = sc.count > 0 ? sc.norm : (double)__builtin_nanf("");
+    if (learning_rate && sc.count == 0) *learning_rate = (double)__builtin_nanf("");  // no step yet
+    return ZF_OK;
+  }
+  int c = 0;
+  ZF_TRY_HIP(hipMemcpy(&c, t->d_bc, sizeof(int), hipMemcpyDeviceToHost));
+  if (count) *count = c;
+  if (learning_rate) *learning_rate = (double)t->opt.learning_rate;
+  if (grad_norm) *grad_norm = (double)__builtin_nanf("");
+  return ZF_OK;
+}
+
+int zf_trainer_set_opt_count(zf_trainer_t* t, int64_t count) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (count < 0 || count > 0x7fffffff) return zf::einval("optimiser count %lld outside [0, 2^31)", (long long)count);
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  if (t->chain_on) {
+    const long long c = count;
+    ZF_TRY_HIP(hipMemcpy(&t->d_osc->count, &c, sizeof(c), hipMemcpyHostToDevice));
+  } else {
+    const int rc = zf::optim_set_count(t->d_bc, (int)count, t->opt.b1, t->opt.b2);
+    if (rc) return rc;
+    ZF_TRY_HIP(hipDeviceSynchronize());
+  }
+  t->t = count;
   return ZF_OK;
 }
 

@@ -65,3 +65,25 @@ def load_variables(path) -> Dict[str, Any]:
     paths); arrays only, nothing executed."""
     with np.load(path, allow_pickle=False) as f:
         return unflatten_variables({k: f[k] for k in f.files})
+
+
+def save_opt_state(path, state: Dict[str, Any]) -> None:
+    """Write ``Trainer.opt_state()`` to ``path`` (.npz): the scalars under
+    their names, moment array k under ``slots/k/<FLAX path>``."""
+    flat = {k: np.asarray(state[k]) for k in ("count", "learning_rate", "grad_norm")}
+    flat["n_slots"] = np.asarray(len(state["slots"]))
+    for k, tree in enumerate(state["slots"]):
+        flat.update(flatten_variables(tree, f"slots{SEP}{k}"))
+    np.savez(path, **flat)
+
+
+def load_opt_state(path) -> Dict[str, Any]:
+    """Read a state written by save_opt_state, for ``Trainer.load_opt_state``."""
+    with np.load(path, allow_pickle=False) as f:
+        flat = {k: f[k] for k in f.files}
+    n = int(flat.pop("n_slots"))
+    state = {"count": int(flat.pop("count")), "learning_rate": float(flat.pop("learning_rate")),
+             "grad_norm": float(flat.pop("grad_norm"))}
+    slots = unflatten_variables(flat).get("slots", {})
+    state["slots"] = [slots[str(k)] for k in range(n)]
+    return state

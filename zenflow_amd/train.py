@@ -13,8 +13,10 @@ Not reproducible offline (no JAX / optax here): jax.random's init and
 permutation streams (seeded numpy generators stand in) and optax's exact
 floating-point order; the optimiser restates optax's published update
 (scale_by_adam with nesterov for nadamw -> add_decayed_weights -> scale by
--learning_rate).  Every gradient element is checked against float64
-autograd of the oracle's loss (oracle/zf_oracle_torch.py,
+-learning_rate), and any other chain of optax's transformations and schedules
+comes from ``zenflow_amd.optim`` and runs on the device too.  Every gradient
+element is checked against float64 autograd of the oracle's loss
+(oracle/zf_oracle_torch.py,
 tests/test_gpu_train.py::test_train_gradient_per_parameter)."""
 
 from __future__ import annotations
@@ -22,13 +24,14 @@ from __future__ import annotations
 import ctypes as ct
 import warnings
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
 from . import _lib as L
 from ._lib import DeviceArray, check
 from .dist import shard_rows
+from .optim import Chain, blob_to_tree, lower_mask, tree_to_blob
 from .random import PRNGKey
 
 
@@ -70,8 +73,12 @@ class Trainer:
     batches of up to ``batch_max`` rows."""
 
     def __init__(self, flow, variables: Dict[str, Any], D: int, C: int, batch_max: int,
-                 optimizer: Optional[Optimizer] = None, comm=None):
-        """``comm``: data parallelism — an object with ``rank``, ``world`` and
+                 optimizer: Union[Optimizer, Chain, None] = None, comm=None):
+        """``optimizer``: an :class:`Optimizer` ((n)adamw at a constant
+        learning rate) or a chain of ``zenflow_amd.optim`` (clipping,
+        schedules, sgd, adam, lion ...), run on the device either way.
+
+        ``comm``: data parallelism — an object with ``rank``, ``world`` and
         ``trainer_comm_desc()`` (``dist.RcclCommunicator``, or
         ``dist.HostAllgather`` for ranks sharing a GPU); each rank then passes
         its shard of every global batch."""
@@ -96,12 +103,25 @@ class Trainer:
 
     def _open(self, prog, comm, keep_program: bool = True):
         self.program = prog if keep_program else None
-        opt = self.optimizer.desc()
+        chain = self.optimizer if isinstance(self.optimizer, Chain) else None
+        lowered = dmask = None
+        if chain is not None:  # rejected chains raise here, before any handle exists
+            lowered = chain.lower()
+            if chain.mask() is not None:
+                dmask = np.ascontiguousarray(lower_mask(chain.mask(), prog), np.uint8)
+        opt = (DEFAULT_OPTIMIZER() if chain is not None else self.optimizer).desc()
         h = ct.c_void_p()
         check(L.load_library().zf_trainer_create(
             ct.byref(prog.desc), prog.blob.ctypes.data, prog.blob.size, prog.param_mask.ctypes.data,
             self.batch_max, ct.byref(opt), ct.byref(h)), "zf_trainer_create")
         self.handle = h.value
+        if chain is not None:
+            rc = L.load_library().zf_trainer_set_optim_chain(
+                self.handle, ct.byref(lowered), None if dmask is None else dmask.ctypes.data)
+            if rc:
+                L.load_library().zf_trainer_destroy(ct.c_void_p(self.handle))
+                self.handle = None
+                check(rc, "zf_trainer_set_optim_chain")
         self._loss = DeviceArray((1,), np.float64)
         self.comm = comm
         self.world = 1
@@ -244,6 +264,41 @@ class Trainer:
         v = self.program.blob_to_variables(blob)
         return {"params": {"bijector": v["params"]}, "batch_stats": {"bijector": v["batch_stats"]}}
 
+    def _n_slots(self) -> int:
+        return self.optimizer.n_slots if isinstance(self.optimizer, Chain) else 2
+
+    def opt_state(self) -> Dict[str, Any]:
+        """The optimiser's state (optax's ``opt_state``): ``count`` (updates
+        applied), the ``learning_rate`` and ``grad_norm`` the last step used
+        (grad_norm NaN without clip_by_global_norm), and ``slots``, the moment
+        arrays as ``params``-shaped trees in chain order (scale_by_adam: mu,
+        nu; scale_by_lion: mu; trace: trace; an :class:`Optimizer`: m, v).
+        With :meth:`variables` it is all a run needs to resume."""
+        lib = L.load_library()
+        count, lr, gn = ct.c_int64(), ct.c_double(), ct.c_double()
+        check(lib.zf_trainer_get_opt_scalars(self.handle, ct.byref(count), ct.byref(lr), ct.byref(gn)),
+              "zf_trainer_get_opt_scalars")
+        slots = []
+        for k in range(self._n_slots()):
+            blob = np.empty(self.program.blob.size, np.float32)
+            check(lib.zf_trainer_get_opt_slot(self.handle, k, blob.ctypes.data), "zf_trainer_get_opt_slot")
+            slots.append(blob_to_tree(self.program, blob))
+        return {"count": int(count.value), "learning_rate": float(lr.value), "grad_norm": float(gn.value),
+                "slots": slots}
+
+    def load_opt_state(self, state: Dict[str, Any]) -> None:
+        """Restore what :meth:`opt_state` returned (of a trainer with the
+        same optimiser): the moments and the step counter, from which the
+        bias corrections and the schedule follow."""
+        lib = L.load_library()
+        slots = list(state["slots"])
+        if len(slots) != self._n_slots():
+            raise ValueError(f"state has {len(slots)} moment arrays, this optimiser keeps {self._n_slots()}")
+        for k, tree in enumerate(slots):
+            blob = np.ascontiguousarray(tree_to_blob(self.program, tree, np.float32))
+            check(lib.zf_trainer_set_opt_slot(self.handle, k, blob.ctypes.data), "zf_trainer_set_opt_slot")
+        check(lib.zf_trainer_set_opt_count(self.handle, int(state["count"])), "zf_trainer_set_opt_count")
+
 
 def _metric(flow, variables, x, c) -> float:
     """metric_fn (train.py:74-78): -mean(log_prob), eval mode."""
@@ -262,7 +317,7 @@ def train(
     *,
     epochs: int = 1000,
     batch_size: int = 1024,
-    optimizer: Optional[Optimizer] = None,
+    optimizer: Union[Optimizer, Chain, None] = None,
     patience: float = 0.05,
     warmup: float = 0.2,
     seed: int = 0,
@@ -274,7 +329,10 @@ def train(
 
     Same arguments, defaults, early stopping and return value
     ``(best_variables, best_epoch, loss_train, loss_test)`` as the reference;
-    ``optimizer`` is an :class:`Optimizer` (``nadamw(...)`` / ``adamw(...)``).
+    ``optimizer`` is an :class:`Optimizer` (``nadamw(...)`` / ``adamw(...)``)
+    or a chain of ``zenflow_amd.optim`` (``optim.chain(optim.clip_by_global_norm(1.0),
+    optim.adamw(optim.warmup_cosine_decay_schedule(...)))``), where the
+    reference takes an ``optax.GradientTransformation``.
 
     ``comm`` (data parallelism, one process per GPU, every rank calling with
     the same data and seed): each global batch of ``batch_size`` rows is cut
