@@ -279,6 +279,22 @@ __global__ __launch_bounds__(256) void latent_sample_kernel(int latent, float pa
 // of 1024 threads, eight independent loads in flight per thread (the
 // 2^20-row NLL has 8192 partials), then a fixed LDS tree.
 constexpr int kReduceThreads = 1024;
+// zf_flow_create: every coupling's KnotConsts from the device's expressions
+// (rnorm is rcp_refined's hardware-reciprocal form, which the host cannot
+// restate), stored with the flow; one lane.
+__global__ __launch_bounds__(64) void knot_consts_kernel(DevFlow* F) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  for (int i = 0; i < F->n_ops; ++i) {
+    const DevOp& op = F->ops[i];
+    if (op.kind != ZF_OP_NSC) continue;
+    const KnotConsts kc(op.K);
+    F->kc[i][0] = kc.c;
+    F->kc[i][1] = kc.norm;
+    F->kc[i][2] = kc.rnorm;
+    F->kc[i][3] = 0.f;
+  }
+}
+
 __global__ __launch_bounds__(kReduceThreads) void reduce_partials(const double* __restrict__ part, long long n,
                                                                   double* __restrict__ out) {
   __shared__ double sm[kReduceThreads];
@@ -688,6 +704,12 @@ int zf_flow_create(const zf_flow_desc* desc_in, const float* blob_host, int64_t 
   if (e == hipSuccess) e = hipMemcpy(h->d_desc, &h->host, sizeof(zf::DevFlow), hipMemcpyHostToDevice);
   if (e == hipSuccess)
     e = hipMemcpy(h->d_blob, h->packed.data(), h->packed.size() * sizeof(float), hipMemcpyHostToDevice);
+  // every coupling's knot constants, from the device's own arithmetic; the host copy of the descriptor takes them too
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(zf::knot_consts_kernel, dim3(1), dim3(64), 0, (hipStream_t) nullptr, h->d_desc);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(&h->host, h->d_desc, sizeof(zf::DevFlow), hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     rcd = zf::hip_status(e, "zf_flow_create");
     zf_flow_destroy(h);
@@ -764,6 +786,14 @@ int launch_flow(zf_flow* h, int op_begin, int op_end, const float* x, const floa
         const int mode = (int)h->packed[(size_t)h->host.ops[i].sb + 8 * j];
         if (mode != ZF_SB_NONE && mode != ZF_SB_BOTH) a.sb_affine = false;
       }
+    }
+    a.par_lit = true;
+    for (int i = op_begin; i < op_end; ++i) {
+      const DevOp& d = h->host.ops[i];
+      if (d.kind != ZF_OP_NSC) continue;
+      if (d.w[0] - d.bn != X3Lit::kW0 || d.b[0] - d.bn != X3Lit::kB0 || d.b[1] - d.b[0] != 128 ||
+          d.x3_blast - d.bn != X3Lit::blast(a.K))
+        a.par_lit = false;
     }
     // the resident form: forced (ZF_X3_RESIDENT=1) or from kX3ResidentAutoRows rows on
     if (h->x3_res_mode != 0 && (h->x3_res_mode == 1 || N >= kX3ResidentAutoRows) &&

@@ -61,6 +61,12 @@ struct DevFlow {
   int _pad;
   float lat_c0, lat_c1, lat_c2, lat_c3;
   DevOp ops[kMaxOps];
+  // softmax_with_threshold's constants of every coupling's K (KnotConsts: c,
+  // norm, rnorm, 0), formed on the device once at zf_flow_create
+  // (knot_consts_kernel) so that the resident form does not divide in fp64
+  // per tile.  Behind the ops: their stride, which every
+  // kernel's code holds as a literal, stays what it was.
+  float kc[kMaxOps][4];
 };
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -141,6 +147,9 @@ __device__ __forceinline__ int wrap(int a, int m) { return a >= m ? a - m : a; }
 // floats (fp64), rounded to fp32 where they meet fp32 arrays.
 struct KnotConsts {
   float c, norm, rnorm;
+  // as stored with the flow (DevFlow::kc; the resident forms' pass head)
+  __device__ __forceinline__ explicit KnotConsts(const float (&k)[4]) : c(k[0]), norm(k[1]), rnorm(k[2]) {}
+  // the expressions themselves (knot_consts_kernel and the streaming kernels)
   __device__ __forceinline__ explicit KnotConsts(int K) {
     const double c64 = 1e-5 / (1.0 - (double)K * 1e-5);
     c = (float)c64;
@@ -359,6 +368,23 @@ __device__ __forceinline__ void flow_epilogue(const DevFlow* __restrict__ F, con
   flow_out_rows(xs, s, hh, rot, D, row, valid, ld, y_out, ld_out);
 }
 
+// The coupling as the resident form's specialised frame runs it (x3_nsc LIT):
+// D = 4, C = 0 (dt = dc = DC = 2, one layer-0 k-step), hidden 128 with one
+// streamed hidden layer, swish, and exactly K real knots.  The shape fixes the
+// layout of the small-parameter region (zf_flow_create: BatchNorm rows,
+// Dense_0, the biases, the permuted last bias), so its offsets are literals
+// (float offsets from op.bn; the host checks them against the handle's,
+// x3_resident_fits), and what is left of the op's scalars — the layer scales,
+// the bound pairs and the knot constants — is read once per pass, not per tile.
+struct X3Lit {
+  static constexpr int kW0 = 8;                 // Dense_0 fragments, behind the 3 x 2 BatchNorm rows
+  static constexpr int kB0 = kW0 + 4 * 64;      // Dense_0's bias; the hidden bias follows it
+  static constexpr int blast(int K) { return kB0 + 2 * 128 + (2 * (3 * K - 1) + 31) / 32 * 32; }
+  float bc, rnorm;  // KnotConsts: c * rnorm, rnorm (both resident frames carry these two through a pass)
+  float rb[2][2];   // DevOp::x3_rb of Dense_0 and Dense_1
+  int kw1, kw_last;
+};
+
 // Host-side entry of the bf16x3 kernel (zf_flow_x3.hip).
 struct X3Launch {
   const DevFlow* desc;
@@ -388,7 +414,10 @@ struct X3Launch {
   // Normal latent, no ld_in): what the caller knows of the flow (sb_affine:
   // every ShiftBounds row of the op range has mode NONE or BOTH), and
   // x3_resident_fits' decision
+  // par_lit: every coupling of the op range keeps its small parameters at the
+  // offsets the frame's literal body assumes (X3Lit)
   bool sb_affine = false;
+  bool par_lit = false;
   int latent = 0;
   bool res_frame = false;
   hipStream_t stream;

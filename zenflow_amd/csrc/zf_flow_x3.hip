@@ -125,14 +125,20 @@ bool x3_resident_fits(const zf_flow_desc& desc, X3Launch& a, bool inverse, int n
   // C = 0, affine ShiftBounds rows only, a Normal latent, no log_det_in —
   // with at most one ShiftBounds in each run of ops between two couplings
   // (the frame keeps one set of its constants before and one behind the
-  // pass's coupling).  Everything else keeps the generic frame.
+  // pass's coupling).  Its coupling body is compiled for that shape alone
+  // (x3_nsc LIT, X3Lit): dt = dc = DC = 2 and one layer-0 k-step follow from
+  // D = 4 and C = 0, one streamed hidden layer and swish are required above,
+  // and here: every coupling of the op range has exactly K real knots (no
+  // padded or mixed knot counts) and its small parameters at X3Lit's offsets
+  // (par_lit).  Everything else keeps the generic frame.
 #ifndef ZF_X3R_FRAME
 #define ZF_X3R_FRAME 1  // tuning: 0 = always the generic frame
 #endif
   a.res_frame = ZF_X3R_FRAME && a.D == 4 && a.C == 0 && a.sb_affine && a.latent == ZF_LATENT_NORMAL &&
-                a.ld_in == nullptr;
+                a.ld_in == nullptr && a.par_lit;
   for (int i = a.op_begin, run = 0; i < a.op_end && a.res_frame; ++i) {
     const int kind = desc.ops[i].kind;
+    if (kind == ZF_OP_NSC && desc.ops[i].knots != a.K) a.res_frame = false;
     run = kind == ZF_OP_NSC ? 0 : run + (kind == ZF_OP_SHIFT_BOUNDS ? 1 : 0);
     if (run > 1) a.res_frame = false;
   }

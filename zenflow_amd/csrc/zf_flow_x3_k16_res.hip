@@ -12,3 +12,11 @@ namespace zf {
 int launch_x3r_k16(const X3Launch& a, bool inverse) { return launch_x3r<16, false>(a, inverse); }
 
 }  // namespace zf
+
+#ifdef ZF_X3_TRACE
+// tuning build only: install the stamp buffer of the resident kernels (n stamps of 8 bytes; null: no stamps)
+extern "C" int zf_x3r_trace_set_k16(void* buf, long long n) {
+  if (hipMemcpyToSymbol(HIP_SYMBOL(zf::x3r_trace_buf), &buf, sizeof(buf)) != hipSuccess) return 1;
+  return hipMemcpyToSymbol(HIP_SYMBOL(zf::x3r_trace_cap), &n, sizeof(n)) == hipSuccess ? 0 : 1;
+}
+#endif

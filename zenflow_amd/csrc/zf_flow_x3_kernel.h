@@ -100,6 +100,22 @@ static_assert(kX3Waves % 4 == 0, "whole 128-row NLL partial slots per block");
 constexpr int kX3TraceSlots = 16;
 __device__ unsigned long long* x3_trace_buf;
 #define X3T_NOW() __builtin_amdgcn_s_memtime()
+// Resident form (flow_kernel_x3r): per block, wave and pass 16 stamps —
+// 0 arrival at the pass's first barrier, 1 exit from it, 2 span DMA issued,
+// 3 exit from the second barrier, 4 the wave's first tile's state ready,
+// 5.. the end of each of its tiles (at most 11) — written as they are taken
+// by lane 0 (a vector store) to the buffer zf_x3r_trace_set_k16 installs;
+// x3r_trace_cap is its length in stamps.
+constexpr int kX3rStamps = 16, kX3rTracePasses = 4;
+__device__ unsigned long long* x3r_trace_buf;
+__device__ long long x3r_trace_cap;
+#define X3R_STAMP(slot)                                                                       \
+  {                                                                                           \
+    const long long i_ = x3r_tix + (slot);                                                    \
+    if (x3r_tb != nullptr && lane == 0 && (slot) < kX3rStamps && i_ < x3r_cap) x3r_tb[i_] = X3T_NOW(); \
+  }
+#else
+#define X3R_STAMP(slot)
 #endif
 // Bytes of one weight group = one 32-row input tile: [s][out tile][part] x 1 KiB.
 template <int NT>
@@ -1254,15 +1270,26 @@ __device__ __forceinline__ void x3_layer(const char* __restrict__ x3, X3Pipe& p,
 // relative to op.bn) and the conditions from the per-wave state (columns D..)
 // — no global load on the per-coupling path, so no vmcnt wait there drains
 // the weight-group DMA in flight.
-template <int T, bool OACT>
+// LIT (the resident form's specialised frame): the shape is X3Lit's, so the
+// k-step loop is one straight-line step and the region offsets are literals.
+template <int T, bool OACT, bool LIT = false>
 __device__ __forceinline__ void x3_layer0(const X3Sc& c, const float* par, const float* xs, int rot, int D,
                                           int s, int hh, int lane, floatx16 (&hb)[T], int swish_tiles,
                                           float* umax = nullptr) {
-  const int dt = c.dt, dc = c.dc, DC = c.DC, KS0 = c.KS0;
+  // the only reads of `c` (an empty placeholder in the literal body) besides c.act in the bf16x3 branch below
+  int dt, dc, DC, KS0;
+  long long w0_rel, b_rel;
+  if constexpr (LIT) {
+    dt = 2; dc = 2; DC = 2; KS0 = 1;
+    w0_rel = X3Lit::kW0; b_rel = X3Lit::kB0;
+  } else {
+    dt = c.dt; dc = c.dc; DC = c.DC; KS0 = c.KS0;
+    w0_rel = c.w0_rel; b_rel = c.b_rel;
+  }
   const int DCp = 2 * KS0;
   const float* bn = par;
-  const float* w0b = par + c.w0_rel;
-  const float* b0 = par + c.b_rel;
+  const float* w0b = par + w0_rel;
+  const float* b0 = par + b_rel;
 #pragma unroll
   for (int o = 0; o < T; ++o) hb[o] = bias_acc(b0 + o * 32, hh);
   for (int ks = 0; ks < KS0; ++ks) {
@@ -1280,6 +1307,7 @@ __device__ __forceinline__ void x3_layer0(const X3Sc& c, const float* par, const
   for (int o = 0; o < T; ++o)
     if (o < swish_tiles) {  // bf16x3 only (f16x2 passes 0)
       if constexpr (OACT) {
+        static_assert(!(OACT && LIT), "the literal body is swish only");
         x3_act_tile<3, true>(hb[o], 1.f, c.act);
       } else {
 #pragma unroll
@@ -1316,7 +1344,16 @@ __device__ __forceinline__ void x3_forward_eval(float x, const RqsBin& b, float&
   const float yv = b.yk + num * rd;                                // :127
   y = b.oob ? x : yv;                                              // :130
   const float num2 = z * (b.dkp1 * z + 2.0f * sk * az) + b.dk * (az * az);  // :133
-  const float sq = (sk + kEps) * rd;
+  // sk + eps takes the rounded slope: never fma(h, rw, eps).  Every kernel
+  // with a runtime dim count has the state store's branch between the two
+  // operations, which keeps them apart; the literal body (x3_nsc LIT) has no
+  // such branch, and all forms must give the same bits.
+  float ske;
+  {
+#pragma clang fp contract(off)
+    ske = sk + kEps;
+  }
+  const float sq = ske * rd;
   const float l = __logf((num2 + kEps) * (sq * sq));
   ld = b.oob ? 0.0f : l;                                           // :138
 }
@@ -1404,7 +1441,7 @@ struct KnotLit {
 // beyond the last knot gives the idx == K fill (NaN width, height and right
 // slope, utils.py:224-230) as rqs_bin_monotone.
 template <bool FWD, int K, bool CR, bool KLIT, int NPV>
-__device__ __forceinline__ RqsBin x3_bin(float v, const float (&P)[NPV], const KnotConsts& kc) {
+__device__ __forceinline__ RqsBin x3_bin(float v, const float (&P)[NPV], float krn, float kbc) {
   float ws[K], hs[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) {
@@ -1421,8 +1458,8 @@ __device__ __forceinline__ RqsBin x3_bin(float v, const float (&P)[NPV], const K
     X[j + 1] = X[j] + ws[j];
     Y[j + 1] = Y[j] + hs[j];
   }
-  const float rn = KLIT ? KnotLit<K>::rnorm : kc.rnorm;
-  const float bc = KLIT ? KnotLit<K>::bc : kc.c * kc.rnorm;
+  const float rn = KLIT ? KnotLit<K>::rnorm : krn;
+  const float bc = KLIT ? KnotLit<K>::bc : kbc;
   const float ax = rcp_refined(X[K]) * rn, ay = rcp_refined(Y[K]) * rn;
 #pragma unroll
   for (int j = 1; j <= K; ++j) {
@@ -1496,6 +1533,13 @@ struct X3Tr {};
 struct X3Tr {};
 #define X3T(k)
 #endif
+// x3_nsc's own phase hooks: the resident form's trace stamps its passes and
+// tiles in flow_kernel_x3r and keeps no phase sums
+#ifdef ZF_X3_TRACE
+#define X3TN(k) if constexpr (!RES) X3T(k)
+#else
+#define X3TN(k) X3T(k)
+#endif
 #ifdef ZF_X3_MARK
 #define X3M(k) asm volatile(";ZFMARK " #k)
 #else
@@ -1506,26 +1550,73 @@ struct X3Tr {};
 // layer 0 from the LDS parameter region `par`, the streamed layers from the
 // weight groups behind `pipe` (RES: from the resident span), the spline on
 // the transformed dims of the per-wave state `xs`, the log-det into `ld`.
-template <int NT, int K, int T, bool PAIRS, bool ONE, bool INV, bool OACT, int ASET, bool RES>
+// RES: the knot constants come from `lit` (bc, rnorm: read at the pass head).
+// LIT: the coupling has X3Lit's shape; the layers are straight-line code and
+// every constant comes from `lit`.  Everything the body takes from `op`, `opc`
+// or `lit` is bound in the block at its head (and the accessors behind
+// it): below that block nothing reads `op` or `opc` directly, so the literal
+// body, whose `opc` is an empty placeholder, cannot pick up a stale field.
+template <int NT, int K, int T, bool PAIRS, bool ONE, bool INV, bool OACT, int ASET, bool RES, bool LIT = false>
 __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const char* __restrict__ x3, X3Pipe& pipe,
                                        const float* par, float* xs, int rot, int D, int s, int hh, int lane,
-                                       float& ld, X3Tr& tr) {
+                                       float& ld, X3Tr& tr, const X3Lit& lit = X3Lit{}) {
+  static_assert(!LIT || (RES && T == 4 && !PAIRS && !ONE && !OACT && NT == 2), "the frame's shape");
   // last-layer tiles per dim pair: 16 parameters per lane half (ONE: 32 of one dim per tile)
   constexpr int TL = ONE ? (3 * K - 1 + 31) / 32 : (3 * K - 1 + 15) / 16;
   constexpr int NPV = ONE ? 32 * TL : 16 * TL;  // spline parameters held per lane
-  const int nh = opc.nh, act = opc.act, dt = opc.dt, kw_last = opc.kw_last;
+  // ---- the coupling's constants: the only reads of op / opc / lit in this function
+  int nh, act, dt, kw1, kw_last;
+  long long b0_rel, blast_rel;
+  float krn, kcc = 0.f, kbc_res = 0.f;  // KnotConsts: rnorm; c (streaming) or c * rnorm as the pass carries it (RES)
+  bool padlast, klit;
+  if constexpr (LIT) {
+    nh = 2; act = ZF_ACT_SWISH; dt = 2;
+    kw1 = lit.kw1; kw_last = lit.kw_last;
+    b0_rel = X3Lit::kB0; blast_rel = X3Lit::blast(K);
+    padlast = false; klit = true;
+    krn = lit.rnorm; kbc_res = lit.bc;
+  } else {
+    // (the fields in the order this function has always read them: another
+    // order renames registers in the streaming kernels)
+    nh = opc.nh; act = opc.act; dt = opc.dt;
+    kw_last = opc.kw_last;
+    if constexpr (RES) {  // the resident form carries them through the pass
+      krn = lit.rnorm; kbc_res = lit.bc;
+    } else {
+      const KnotConsts kc(opc.kreal);
+      krn = kc.rnorm; kcc = kc.c;
+    }
+    padlast = opc.kreal == K - 1;
+    klit = opc.kreal == K;  // x3_bin: the knot constants as literals
+    b0_rel = opc.b_rel; blast_rel = opc.blast_rel;
+    kw1 = opc.kw1;
+  }
+  // c * rnorm, the one accessor of kcc / kbc_res.  The streaming form multiplies
+  // where the product is used, as it always has: formed up here it reschedules
+  // every streaming kernel (6,453 lines of the K = 16 unit's assembly), and
+  // their code is held to the parent's.
+  const auto kbc = [&]() -> float {
+    if constexpr (RES) return kbc_res;
+    else return kcc * krn;
+  };
+  // DevOp::x3_rb[l][j] and x3_kw[l] of the layers the loops below index at run time
+  const auto rb = [&](int l, int j) -> float {
+    if constexpr (LIT) return lit.rb[l & 1][j];
+    else return op.x3_rb[l][j];
+  };
+  const auto kwl = [&](int l) -> int {
+    if constexpr (LIT) return l == 1 ? lit.kw1 : lit.kw_last;
+    else return op.x3_kw[l];
+  };
+  // ----
   // this coupling's knots: a chain may mix knot counts up to the kernel's K
   // (x3_padded_knots); K - 1 real knots put the idx == K sliver at the
   // padded knot (rqs_bin_monotone padlast)
-  const KnotConsts kc(opc.kreal);
-  const bool padlast = opc.kreal == K - 1;
 #ifdef ZF_X3_MARK
-  const bool klit = true;  // marker builds: count one x3_bin copy
-#else
-  const bool klit = opc.kreal == K;  // x3_bin: the knot constants as literals
+  klit = true;  // marker builds: count one x3_bin copy
 #endif
   // hidden biases are consecutive T x 32 blocks after Dense_0's (zf_flow.hip: b[l] = b[0] + l T 32)
-  const long long b_rel = opc.b_rel + T * 32, blast_rel = opc.blast_rel;
+  const long long b_rel = b0_rel + T * 32;
   floatx16 hb[T];
   // The swish of a layer's output is deferred tile by tile into the next
   // streamed layer (x3_step, SW) — except before a PAIRS last layer,
@@ -1551,15 +1642,15 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
 #endif
   constexpr int kPreSP = (!ZF_X3_PRESP || !kEarly) ? 0 : !ONE ? K / 8 : (K == 16 ? 1 : 0);
   float umax = 0.f;
-  x3_layer0<T, OACT>(opc, par, xs, rot, D, s, hh, lane, hb, NT == 2 ? 0 : (!OACT && (nh > 1 || kLastSW)) ? 1 : T,
+  x3_layer0<T, OACT, LIT>(opc, par, xs, rot, D, s, hh, lane, hb, NT == 2 ? 0 : (!OACT && (nh > 1 || kLastSW)) ? 1 : T,
                      kEarly ? &umax : nullptr);
   float eU = 0.f, eisc = 1.f, eus = 1.f, eius = 1.f;  // kEarly: bound and scales of the current layer input
   halfx8 ecs[2];  // kEarly: k-step-0 split of the current layer input's tile 0
   if constexpr (kEarly) {
     const X3Halves uq = x3_halves(umax);
     umax = fmaxf(uq.lo, uq.hi);
-    eU = __builtin_fmaf(op.x3_rb[0][0], umax, op.x3_rb[0][1]);
-    x3_scale_from(eU, nh > 1 ? opc.kw1 : kw_last, eisc, eus, eius);
+    eU = __builtin_fmaf(rb(0, 0), umax, rb(0, 1));
+    x3_scale_from(eU, nh > 1 ? kw1 : kw_last, eisc, eus, eius);
     x3_act_tile<NT, false>(hb[0], eisc, act);
     split8h<0>(hb[0], ecs[0], ecs[1]);
   }
@@ -1605,15 +1696,15 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
 #if ZF_X3_ABL != 4  // tuning ablation 4: no issue priority
   if constexpr (T == 4) __builtin_amdgcn_s_setprio(2);
 #endif
-  X3T(1);
+  X3TN(1);
   if constexpr (kEarly) {
     float eM = eU;  // max |v'| of the current layer input's pre-activations (exact from layer 2 on)
     for (int l = 1; l < nh; ++l) {
       // the next layer's input bound and scales (its tile 0 is swished in this layer's last
       // step), from the exact maximum of this layer's input, so bounds never compound
-      const float nU = __builtin_fmaf(op.x3_rb[l][0], eM, op.x3_rb[l][1]);
+      const float nU = __builtin_fmaf(rb(l, 0), eM, rb(l, 1));
       float nisc, nus, nius;
-      x3_scale_from(nU, l + 1 < nh ? op.x3_kw[l + 1] : kw_last, nisc, nus, nius);
+      x3_scale_from(nU, l + 1 < nh ? kwl(l + 1) : kw_last, nisc, nus, nius);
       floatx16 acc[T];
 #pragma unroll
       for (int o = 0; o < T; ++o) acc[o] = floatx16{0};
@@ -1631,7 +1722,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
     floatx16 acc[T];
     float isc = 1.f, us = 1.f, ius = 1.f;
     if constexpr (NT == 2) {
-      x3_act_scale<T, OACT>(hb, l == 1 ? opc.kw1 : op.x3_kw[l], isc, us, ius, act);
+      x3_act_scale<T, OACT>(hb, l == 1 ? kw1 : kwl(l), isc, us, ius, act);
       // OACT: every tile here, outside the MFMA stream (the switch there
       // would cost a third of the waves)
 #pragma unroll
@@ -1673,7 +1764,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
       }
     }
   }
-  X3T(2);
+  X3TN(2);
   // Last Dense (:346-347), one pair of transformed dims at a time: lane
   // half h, tile o, register r = parameter 16*o + r of dim 2*pair + h.
   float ldn = 0.f;  // this coupling's log-det, summed in dim order (utils.py:139)
@@ -1716,7 +1807,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
 #pragma unroll
     for (int o = 0; o < TL; ++o)
       pa[o] = kSeed ? bias_acc(bl + o * 32, hh) : (kSeedScaled ? bias_acc(bl + o * 32, hh) * lius : floatx16{0});
-    X3T(3);
+    X3TN(3);
     if constexpr (kEarly) {
       float mx;
       x3_layer_early<T, TL, false, kPreSP, 0, RES>(x3, pipe, hb, pa, lane, bl, hh, ecs, lisc, lus, 0.f, mx);
@@ -1737,7 +1828,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
       for (int o = 0; o < TL; ++o) pa[o] *= lus;
     }
     if constexpr (T == 4) __builtin_amdgcn_s_setprio(0);
-    X3T(4);
+    X3TN(4);
     // ONE at K = 16: tile 0 holds the widths on lane half 0 and the
     // heights on half 1, so each half normalises its own 16 (squareplus,
     // sum in order, quotients: the same operations per value) and one
@@ -1784,13 +1875,13 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
       bool binned = false;
       if constexpr (ZF_X3_BSEARCH && !kSplitWH && !kPreSP && (K == 8 || K == 16 || K == 32 || K == 64)) {
         if (klit) {  // the halving search takes unpadded knots only, not yet squareplus'd ones
-          bin = x3_bin<!INV, K, OACT, true>(xv, P, kc);
+          bin = x3_bin<!INV, K, OACT, true>(xv, P, krn, kbc());
           binned = true;
         }
       }
       if (!binned) {
         float w[K], hg[K];
-        const float bc = kc.c * kc.rnorm;
+        const float bc = kbc();
         if constexpr (kSplitWH) {
           float sw = 0.f;  // half 0: the widths' sum, half 1: the heights'
 #pragma unroll
@@ -1798,7 +1889,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
             w[j] = kPreSP ? P[j] : x3_squareplus2_t<OACT>(P[j]);
             sw = sw + w[j];
           }
-          const float a = rcp_refined(sw) * kc.rnorm;
+          const float a = rcp_refined(sw) * krn;
 #pragma unroll
           for (int j = 0; j < K; ++j) {
             const X3Halves q = x3_halves(__builtin_fmaf(w[j], a, bc));
@@ -1818,7 +1909,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
           // 2*squareplus: the same quotient bits): the parameters
           // themselves already differ from the reference's in the last ulp
           // (GEMM summation order), so correctly rounded divisions buy nothing.
-          const float ax = rcp_refined(sx) * kc.rnorm, ay = rcp_refined(sy) * kc.rnorm;
+          const float ax = rcp_refined(sx) * krn, ay = rcp_refined(sy) * krn;
 #pragma unroll
           for (int j = 0; j < K; ++j) {
             w[j] = __builtin_fmaf(w[j], ax, bc);
@@ -1856,7 +1947,7 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
     }
   }
   if (!INV) ld = ld + ldn;  // Chain: log_det += ld (bijectors.py:110)
-  X3T(5);
+  X3TN(5);
 }
 
 // Resident form (f16x2, hidden 128, one streamed hidden layer, one dim pair):
@@ -2057,6 +2148,11 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
   pipe.par_dst = nullptr;
   pipe.par_pieces = 0;
   X3Tr tr = {};
+#ifdef ZF_X3_TRACE
+  unsigned long long* const x3r_tb = x3r_trace_buf;
+  const long long x3r_cap = x3r_trace_cap;
+  int x3r_pass = 0;
+#endif
   const int nq = op_end - op_begin;
   int rot0 = 0;  // the roll rotation at the start of the pass (the same for every row)
   bool first = true;
@@ -2103,15 +2199,41 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
       }
       fr_pack = X3rPass::pack(fr_rota, fr_rotb, fr_rotn, rot, fr_sba >= 0, fr_sbb >= 0, fr_nsc);
     }
+#ifdef ZF_X3_TRACE
+    const long long x3r_tix = x3r_pass < kX3rTracePasses
+                                  ? (((long long)blockIdx.x * NW + wave) * kX3rTracePasses + x3r_pass) * kX3rStamps
+                                  : x3r_cap;  // later passes: no stamps
+    ++x3r_pass;
+#endif
+    X3R_STAMP(0);
     // every wave of every block passes these two barriers once per pass, whatever its tile list
     __syncthreads();  // all waves are done with the previous coupling's weights
+    X3R_STAMP(1);
     if (nsc >= 0 && nt > 0) {
       const DevOp& fo = F->ops[INV ? (op_end - 1 - nsc) : (op_begin + nsc)];
       const int pieces = (T * (fo.n_hidden - 1) * group_bytes<NT>(T) + T * group_bytes<NT>(fo.x3_tlast)) >> 10;
       x3_dma(x3 + fo.x3, lds, pieces, wave, lane, NW);
       x3_dma(reinterpret_cast<const char*>(blob + fo.bn), par_lds, fo.x3_par_pieces, wave, lane, NW);
     }
+    X3R_STAMP(2);
+    // The coupling's knot constants as stored with the flow (DevFlow::kc),
+    // read here once per pass for either frame: no tile divides in fp64.
+    // FR: and what else the literal body takes from its op (X3Lit), carried
+    // in scalar registers, so that its tile loop has no scalar load.
+    X3Lit lit = {};
+    if (nsc >= 0) {
+      const KnotConsts kc(F->kc[INV ? (op_end - 1 - nsc) : (op_begin + nsc)]);
+      lit.bc = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(kc.c * kc.rnorm)));
+      lit.rnorm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(kc.rnorm)));
+    }
     if constexpr (FR) {
+      if (nsc >= 0) {
+        const DevOp& fo = F->ops[INV ? (op_end - 1 - nsc) : (op_begin + nsc)];
+        lit.rb[0][0] = fo.x3_rb[0][0]; lit.rb[0][1] = fo.x3_rb[0][1];
+        lit.rb[1][0] = fo.x3_rb[1][0]; lit.rb[1][1] = fo.x3_rb[1][1];
+        lit.kw1 = fo.x3_kw[1];
+        lit.kw_last = fo.x3_kw[2];
+      }
       int lh = lane;  // an opaque copy: the pass head's per-lane addresses are formed here, not kept
       asm volatile("" : "+v"(lh));
       if (wave == 0 && lh < 8) {
@@ -2121,6 +2243,7 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // the span and the parameters are complete
+    X3R_STAMP(3);
 
     int cur = 0;
     if (!first && wave < nt) x3r_fetch(state + (tile0 + wave) * ST, xs0, D, DS, lane);
@@ -2150,7 +2273,8 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
             const float lat_c3 = F->lat_c3;
             const float* xt = xin + tile * (kTile * 4);
 #pragma unroll
-            for (int d = h1; d < 4; d += 2) {
+            for (int e = 0; e < 2; ++e) {  // this half's two dims, written out: no loop on the opaque lane half
+              const int d = h1 + 2 * e;
               float v = 0.f;
               if (valid1) v = (INV && gen) ? latent_draw(ZF_LATENT_NORMAL, lat_c3, seed, row1, d) : xt[s1 * 4 + d];
               xs[d * 32 + s1] = v;
@@ -2166,6 +2290,9 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
         for (int j = h1; j < C; j += 2) xs[(D + j) * 32 + s1] = valid1 ? cin[row1 * C + j] : 0.f;
       }
       wave_lds_sync();
+#ifdef ZF_X3_TRACE
+      if (t == wave) X3R_STAMP(4);
+#endif
       float ld;
       if (first) {
         const long long row1 = tile * kTile + (ln & 31);
@@ -2180,15 +2307,15 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
         asm volatile("" : "+s"(fp));
         if (X3rPass::has_sb_before(fp)) x3r_shift_bounds<INV>(sbk, xs, s, hh, X3rPass::rot_sb_before(fp), ld);
         {
-          const DevOp& op = F->ops[X3rPass::nsc(fp)];
-          const X3Sc opc = x3_scalars<INV>(op);
+          const DevOp& op = F->ops[X3rPass::nsc(fp)];  // a reference only: the literal body loads nothing from it
+          const X3Sc opc = {};                         // an empty placeholder (x3_nsc's head block)
           int zoff = 0;
           asm volatile("" : "+s"(zoff));
           pipe.cur = lds + zoff;
           pipe.g = 0;
-          x3_nsc<NT, K, T, false, ONE, INV, false, 0, true>(
-              op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, X3rPass::rot_nsc(fp), 4, s, hh, lane, ld,
-              tr);
+          x3_nsc<NT, K, T, false, ONE, INV, false, 0, true, FR>(
+              op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, X3rPass::rot_nsc(fp), 4, s, hh,
+              lane, ld, tr, lit);
         }
         asm volatile("" : "+s"(fp));
         if (X3rPass::has_sb_after(fp)) x3r_shift_bounds<INV>(sbk + 4, xs, s, hh, X3rPass::rot_sb_after(fp), ld);
@@ -2210,7 +2337,7 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
             pipe.cur = lds + zoff;
             pipe.g = 0;
             x3_nsc<NT, K, T, false, ONE, INV, false, 0, true>(
-                op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, rot, D, s, hh, lane, ld, tr);
+                op, opc, x3, pipe, reinterpret_cast<const float*>(par_lds + zoff), xs, rot, D, s, hh, lane, ld, tr, lit);
           }
         }
       }
@@ -2225,7 +2352,7 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
         float* st = state + tile * ST;
         if constexpr (FR) {
 #pragma unroll
-          for (int d = h2; d < 4; d += 2) st[d * 32 + s2] = xs[d * 32 + s2];
+          for (int e = 0; e < 2; ++e) st[(h2 + 2 * e) * 32 + s2] = xs[(h2 + 2 * e) * 32 + s2];
         } else {
 #pragma nounroll
           for (int d = h2; d < D; d += 2) st[d * 32 + s2] = xs[d * 32 + s2];
@@ -2240,7 +2367,7 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
         if (y_out != nullptr && valid) {
           float* yt = y_out + tile * (kTile * 4);
 #pragma unroll
-          for (int j = h2; j < 4; j += 2) yt[s2 * 4 + j] = xs[((j + rot) & 3) * 32 + s2];
+          for (int e = 0; e < 2; ++e) yt[s2 * 4 + h2 + 2 * e] = xs[((h2 + 2 * e + rot) & 3) * 32 + s2];
         }
         if (ld_out != nullptr && valid && h2 == 0) (ld_out + tile * kTile)[s2] = ld;
       } else {
@@ -2251,6 +2378,9 @@ __global__ __launch_bounds__(kX3ResWaves * 64, 1) void flow_kernel_x3r(
         flow_out_rows(xs, s2, h2, rot, D, row, valid, ld, y_out, ld_out);
       }
       wave_lds_sync();
+#ifdef ZF_X3_TRACE
+      X3R_STAMP(5 + (t - wave) / NW);
+#endif
       cur ^= 1;
     }
     for (int r = q; r < seg_end; ++r) {

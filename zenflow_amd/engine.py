@@ -150,7 +150,8 @@ class Program:
     def launch_count(self, form: str) -> int:
         """Launches of the split-MFMA kernels this program has made in one form: 'streaming',
         'resident' (the resident form's generic frame) or 'resident_frame' (its frame specialised
-        for D = 4, C = 0, affine ShiftBounds and a Normal latent; zf_flow_launch_count)."""
+        for D = 4, C = 0, affine ShiftBounds, a Normal latent and couplings that all have exactly
+        the kernel's knot count, no padded or mixed ones; zf_flow_launch_count)."""
         f = {"streaming": L.ZF_FORM_STREAMING, "resident": L.ZF_FORM_RESIDENT,
              "resident_frame": L.ZF_FORM_RESIDENT_FRAME}[form]
         return int(L.load_library().zf_flow_launch_count(ct.c_void_p(self.handle), f))
