@@ -131,10 +131,7 @@ bool x3_resident_fits(const zf_flow_desc& desc, X3Launch& a, bool inverse, int n
   // and here: every coupling of the op range has exactly K real knots (no
   // padded or mixed knot counts) and its small parameters at X3Lit's offsets
   // (par_lit).  Everything else keeps the generic frame.
-#ifndef ZF_X3R_FRAME
-#define ZF_X3R_FRAME 1  // tuning: 0 = always the generic frame
-#endif
-  a.res_frame = ZF_X3R_FRAME && a.D == 4 && a.C == 0 && a.sb_affine && a.latent == ZF_LATENT_NORMAL &&
+  a.res_frame = a.D == 4 && a.C == 0 && a.sb_affine && a.latent == ZF_LATENT_NORMAL &&
                 a.ld_in == nullptr && a.par_lit;
   for (int i = a.op_begin, run = 0; i < a.op_end && a.res_frame; ++i) {
     const int kind = desc.ops[i].kind;

@@ -37,6 +37,12 @@
 // Large batches of the shapes x3_resident_fits names run the resident form
 // flow_kernel_x3r below instead: the same per-row code (x3_nsc), coupling-major,
 // with a coupling's whole weight span kept in LDS.
+//
+// Build-time macros: only two, neither set in the shipped library and neither
+// changing a result — ZF_X3_TRACE (the phase trace and the resident stamp
+// trace, with the ZF_X3_LDS_PAD occupancy probe under it) and ZF_X3_MARK
+// (marker comments in the assembly for scripts/valu_budget.py).  Every other
+// tuning toggle and ablation was folded to its measured default.
 #pragma once
 #include "zf_flow_dev.h"
 
@@ -84,18 +90,12 @@ struct XT<2> {
 // per MFMA (measured +4-5% at cfg5; at T = 4 both were neutral to -12%).
 constexpr int kWideSched = 3;
 
-#ifndef ZF_X3_WAVES
-#define ZF_X3_WAVES 4
-#endif
-constexpr int kX3Waves = ZF_X3_WAVES;  // waves per block: 32 samples each
+constexpr int kX3Waves = 4;  // waves per block: 32 samples each
 static_assert(kX3Waves % 4 == 0, "whole 128-row NLL partial slots per block");
 
 // Tuning-only phase trace (a separate build with -DZF_X3_TRACE=1, never the
 // shipped library): each wave sums s_memtime ticks per phase and writes them
 // at exit (lane 0, vector stores) to the buffer zf_x3_trace_set_k* installs.
-#ifndef ZF_X3_ABL
-#define ZF_X3_ABL 0  // tuning-only ablations (wrong results), never set in the shipped build
-#endif
 #ifdef ZF_X3_TRACE
 constexpr int kX3TraceSlots = 16;
 __device__ unsigned long long* x3_trace_buf;
@@ -570,9 +570,6 @@ __device__ __forceinline__ X3Span make_span(const X3Sc& c, bool has_next) {
 // spread over the block's waves.
 __device__ __forceinline__ void x3_dma(const char* __restrict__ src, char* dst, int pieces, int wave, int lane,
                                        int nw = kX3Waves) {
-#if ZF_X3_ABL == 5  // tuning ablation 5: a quarter of the weight stream (wrong results)
-  pieces = (pieces + 3) / 4;
-#endif
   for (int p = wave; p < pieces; p += nw)
     __builtin_amdgcn_global_load_lds((const void*)(src + (p << 10) + lane * 16),
                                      (__attribute__((address_space(3))) void*)(dst + (p << 10)), 16, 0, 0);
@@ -604,9 +601,6 @@ __device__ __forceinline__ void x3_issue_next(const char* __restrict__ x3, const
   constexpr int kHid = group_bytes<NT>(T);
   if (p.g == 0 && p.par_src != nullptr) x3_dma(p.par_src, p.par_dst, p.par_pieces, p.wave, lane);
   const int g = p.g + 1;
-#if ZF_X3_ABL == 6  // tuning ablation 6: the stream stops after each NSC's first two groups (real weights stay; wrong results)
-  if (g > 1 && g < p.span.G) return;
-#endif
   long long off;
   int pieces;
   if (g < p.span.nhid) {
@@ -720,10 +714,8 @@ __device__ __forceinline__ void x3_step_pipe(const char* __restrict__ x3, X3Pipe
 #ifdef ZF_X3_TRACE
   const unsigned long long tb0 = X3T_NOW();
 #endif
-#if ZF_X3_ABL != 3  // tuning ablation 3: no per-group DMA wait / barrier (wrong results)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-#endif
 #ifdef ZF_X3_TRACE
   p.tbar += X3T_NOW() - tb0;
 #endif
@@ -731,37 +723,23 @@ __device__ __forceinline__ void x3_step_pipe(const char* __restrict__ x3, X3Pipe
   const char* lb = p.cur + lane * 16;
   E s1[NT];
   splitk<NT, 1>(hb[Q], s1);
-#if ZF_X3_ABL == 1  // tuning ablation 1: one A fragment per step (no per-tile LDS reads; wrong results)
-  E a1[NT];
-  load_frag<NT>(lb, a1);
-#endif
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) {
-#if ZF_X3_ABL == 1
-    acc[o] = mfma_split<NT>(a1, cs, acc[o]);
-#else
     E a[NT];
     load_frag<NT>(lb + ((o * NT) << 10), a);
     acc[o] = mfma_split<NT>(a, cs, acc[o]);
-#endif
   }
   if constexpr (Q + 1 < T) {
-#if ZF_X3_ABL != 2  // tuning ablation 2: no swish inside the group steps (wrong results)
     // OACT with a narrowed activation set (AS, f16x2): tile Q+1's activation
     // here too, beside this group's MFMAs (not serially at the layer end)
     if constexpr (!OACT || (NT == 2 && AS != 0)) x3_act_tile<NT, OACT, AS>(hb[Q + 1], isc, act);
-#endif
     splitk<NT, 0>(hb[Q + 1], cs);
   }
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) {
-#if ZF_X3_ABL == 1
-    acc[o] = mfma_split<NT>(a1, s1, acc[o]);
-#else
     E a[NT];
     load_frag<NT>(lb + (((NOUT + o) * NT) << 10), a);
     acc[o] = mfma_split<NT>(a, s1, acc[o]);
-#endif
   }
   if constexpr (HASB) {
     // the layer end, acc * us + bias; each bias tile read as it is used, after
@@ -827,13 +805,6 @@ __device__ __forceinline__ void x3_slot(const char* lb, floatx16 (&hb)[T], float
   if constexpr (ks == 0) acc[o] = mfma_term2(fr[t & 1], cs, j, acc[o]);
   else acc[o] = mfma_term2(fr[t & 1], s1, j, acc[o]);
   x3_valu_slot<T, NOUT, Q, m>(hb, cs, s1, tq, s1h, csh, c);
-#if ZF_X3_ABL == 12 || ZF_X3_ABL == 13  // tuning: extra VALU in the group slots (12: v_add, 13: v_exp), 8 per group
-  if constexpr (j == 0) {
-    float dd;
-    if (ZF_X3_ABL == 12) asm volatile("v_add_f32 %0, %1, %2" : "=v"(dd) : "v"(acc[o][0]), "v"(acc[o][1]));
-    else asm volatile("v_exp_f32 %0, %1" : "=v"(dd) : "v"(acc[o][0]));
-  }
-#endif
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -1056,108 +1027,6 @@ __device__ __forceinline__ void x3_step_slots_last(const char* __restrict__ x3, 
   x3_advance<RES, group_bytes<2>(NOUT)>(p);
 }
 
-// Fused swish + split (ZF_X3_FUSED): the hi / lo fp16 terms of the exact
-// product v' * r of act_swish (one rounding each, v_fma_mix{lo,hi}: hi =
-// RN16(v' r), lo = RN16(v' r - hi)) instead of the fp32 product, a
-// conversion and the residual: 2 VALU per value instead of 2.5.  Value 2p of
-// a k-step goes to the low halves of h[p] / l[p], value 2p + 1 to the high
-// halves.  Their consumers are MFMAs of the next group step (behind its
-// barrier), so no hazard pad is needed here.
-template <int ODD>
-__device__ __forceinline__ void mix_hi(uint32_t& h, float v, float r) {
-  if constexpr (ODD == 0) asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(v), "v"(r));
-  else asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(v), "v"(r));
-}
-template <int ODD>
-__device__ __forceinline__ void mix_lo(uint32_t& l, float v, float r, uint32_t h) {
-  if constexpr (ODD == 0)
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(v), "v"(r), "v"(h));
-  else
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(v), "v"(r), "v"(h));
-}
-
-// Slot m's VALU in the fused schedule: Q == 0 splits its k-step 1 at slots
-// 0 / 1 (tile 0 arrives swished in fp32); tile Q+1 runs as a 5-stage modulo
-// pipeline, value i: exp at slot i+1, fma at i+2, rcp at i+3, hi at i+4, lo
-// at i+5, into nh / nl (pairs 0-3: k-step 0, 4-7: k-step 1).
-template <int T, int NOUT, int Q, int m>
-__device__ __forceinline__ void x3_valu_slot_f(floatx16 (&hb)[T], halfx8 (&s1)[2], uint32_t (&s1h)[4],
-                                               float (&tq)[5], uint32_t (&nh)[8], uint32_t (&nl)[8], float c) {
-  if constexpr (Q == 0 && m == 0) split8h_hi<1>(hb[0], s1h);
-  if constexpr (Q == 0 && m == 1) split8h_lo<1>(hb[0], s1h, s1[0], s1[1]);
-  if constexpr (Q + 1 < T) {
-    constexpr int i0 = m - 1, i1 = m - 2, i2 = m - 3, i3 = m - 4, i4 = m - 5;
-    if constexpr (i4 >= 0 && i4 < 16) mix_lo<i4 & 1>(nl[i4 >> 1], hb[Q + 1][i4], tq[i4 % 5], nh[i4 >> 1]);
-    if constexpr (i3 >= 0 && i3 < 16) mix_hi<i3 & 1>(nh[i3 >> 1], hb[Q + 1][i3], tq[i3 % 5]);
-    if constexpr (i2 >= 0 && i2 < 16) tq[i2 % 5] = __builtin_amdgcn_rcpf(tq[i2 % 5]);
-    if constexpr (i1 >= 0 && i1 < 16) tq[i1 % 5] = __builtin_fmaf(tq[i1 % 5], c, c);
-    if constexpr (i0 >= 0 && i0 < 16) tq[i0 % 5] = __builtin_amdgcn_exp2f(-hb[Q + 1][i0]);
-  }
-}
-
-template <int T, int NOUT, int Q, int m>
-__device__ __forceinline__ void x3_slot_f(const char* lb, floatx16 (&hb)[T], floatx16 (&acc)[NOUT],
-                                          halfx8 (&fr)[2][2], halfx8 (&cs)[2], halfx8 (&s1)[2], uint32_t (&s1h)[4],
-                                          float (&tq)[5], uint32_t (&nh)[8], uint32_t (&nl)[8], float c) {
-  constexpr int t = m / 3, j = m % 3, ks = t / NOUT, o = t % NOUT;
-  if constexpr (j == 0 && t + 1 < 2 * NOUT) load_frag<2>(lb + (((t + 1) * 2) << 10), fr[(t + 1) & 1]);
-  if constexpr (ks == 0) acc[o] = mfma_term2(fr[t & 1], cs, j, acc[o]);
-  else acc[o] = mfma_term2(fr[t & 1], s1, j, acc[o]);
-  x3_valu_slot_f<T, NOUT, Q, m>(hb, s1, s1h, tq, nh, nl, c);
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int T, int NOUT, int Q, int... M>
-__device__ __forceinline__ void x3_slots_all_f(std::integer_sequence<int, M...>, const char* lb, floatx16 (&hb)[T],
-                                               floatx16 (&acc)[NOUT], halfx8 (&fr)[2][2], halfx8 (&cs)[2],
-                                               halfx8 (&s1)[2], uint32_t (&s1h)[4], float (&tq)[5],
-                                               uint32_t (&nh)[8], uint32_t (&nl)[8], float c) {
-  (x3_slot_f<T, NOUT, Q, M>(lb, hb, acc, fr, cs, s1, s1h, tq, nh, nl, c), ...);
-}
-
-template <int T, int NOUT, int Q, int... M>
-__device__ __forceinline__ void x3_valu_tail_f(std::integer_sequence<int, M...>, floatx16 (&hb)[T], halfx8 (&s1)[2],
-                                               uint32_t (&s1h)[4], float (&tq)[5], uint32_t (&nh)[8],
-                                               uint32_t (&nl)[8], float c) {
-  (x3_valu_slot_f<T, NOUT, Q, 2 * NOUT * 3 + M>(hb, s1, s1h, tq, nh, nl, c), ...);
-}
-
-// x3_step_slots with the fused swish + split: cs / s1 hold tile Q's k-step
-// 0 / 1 terms (s1 formed here for Q == 0), and leave tile Q+1's.
-template <int T, int NOUT, int Q, bool HASB>
-__device__ __forceinline__ void x3_step_slots_f(const char* __restrict__ x3, X3Pipe& p, floatx16 (&hb)[T],
-                                                floatx16 (&acc)[NOUT], int lane, const float* __restrict__ bias,
-                                                int hh, halfx8 (&cs)[2], halfx8 (&s1)[2], float isc, float us) {
-  constexpr int NT = 2;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  x3_issue_next<NT, T>(x3, p, p.nxt, lane);
-  const char* lb = p.cur + lane * 16;
-  halfx8 fr[2][NT];
-  load_frag<NT>(lb, fr[0]);
-  constexpr int kSlots = 2 * NOUT * 3;
-  float tq[5];
-  uint32_t s1h[4], nh[8], nl[8];
-  x3_slots_all_f<T, NOUT, Q>(std::make_integer_sequence<int, kSlots>{}, lb, hb, acc, fr, cs, s1, s1h, tq, nh, nl,
-                             isc);
-  x3_valu_tail_f<T, NOUT, Q>(std::make_integer_sequence<int, (kSlots < 21 ? 21 - kSlots : 0)>{}, hb, s1, s1h, tq,
-                             nh, nl, isc);
-  if constexpr (HASB) {
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) acc[o] = x3_finish<NT>(acc[o], us, bias_acc(bias + o * 32, hh));
-  }
-  if constexpr (Q + 1 < T) {
-    __builtin_memcpy(&cs[0], &nh[0], 16);
-    __builtin_memcpy(&cs[1], &nl[0], 16);
-    __builtin_memcpy(&s1[0], &nh[4], 16);
-    __builtin_memcpy(&s1[1], &nl[4], 16);
-  }
-  char* const t = p.cur;
-  p.cur = p.nxt;
-  p.nxt = t;
-  p.g += 1;
-}
-
 // Dim-pair last layer (PAIRS, f16x2): the layer input is split once, before
 // the pair loop (sp[tile][k-step] = hi / lo), so each pair's group steps are
 // MFMAs and fragment reads only (the plain steps re-split every tile per
@@ -1201,27 +1070,11 @@ __device__ __forceinline__ void x3_layer_pre(const char* __restrict__ x3, X3Pipe
 template <int NT, int T, int NOUT, bool HASB, bool OACT, int Q = 0, int AS = 0>
 __device__ __forceinline__ void x3_layer_pipe(const char* __restrict__ x3, X3Pipe& p, floatx16 (&hb)[T],
                                               floatx16 (&acc)[NOUT], int lane, const float* bias_last, int hh,
-                                              typename XT<NT>::E (&cs)[NT], float isc, float us, int act,
-                                              halfx8 (&fused_s1)[2]) {
-#ifndef ZF_X3_FUSED
-#define ZF_X3_FUSED 0
-#endif
-  if constexpr (NT == 2 && !OACT && ZF_X3_FUSED) {  // the swish kernels, fused swish + split
-    static_assert(sizeof(typename XT<NT>::E) == 16, "halfx8 terms");
-    halfx8(&s1)[2] = fused_s1;
-    if constexpr (Q + 1 < T) {
-      x3_step_slots_f<T, NOUT, Q, false>(x3, p, hb, acc, lane, nullptr, hh, cs, s1, isc, us);
-      x3_layer_pipe<NT, T, NOUT, HASB, OACT, Q + 1>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us, act, s1);
-    } else {
-      x3_step_slots_f<T, NOUT, Q, HASB>(x3, p, hb, acc, lane, bias_last, hh, cs, s1, isc, us);
-    }
-    return;
-  }
+                                              typename XT<NT>::E (&cs)[NT], float isc, float us, int act) {
   if constexpr (NT == 2 && !OACT) {  // the swish kernels: explicit MFMA slots (x3_step_slots)
     if constexpr (Q + 1 < T) {
       x3_step_slots<T, NOUT, Q, false>(x3, p, hb, acc, lane, nullptr, hh, cs, isc, us);
-      x3_layer_pipe<NT, T, NOUT, HASB, OACT, Q + 1>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us, act,
-                                                    fused_s1);
+      x3_layer_pipe<NT, T, NOUT, HASB, OACT, Q + 1>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us, act);
     } else {
       x3_step_slots<T, NOUT, Q, HASB>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us);
     }
@@ -1229,8 +1082,7 @@ __device__ __forceinline__ void x3_layer_pipe(const char* __restrict__ x3, X3Pip
   }
   if constexpr (Q + 1 < T) {
     x3_step_pipe<NT, T, NOUT, Q, false, OACT, AS>(x3, p, hb, acc, lane, nullptr, hh, cs, isc, us, act);
-    x3_layer_pipe<NT, T, NOUT, HASB, OACT, Q + 1, AS>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us, act,
-                                                      fused_s1);
+    x3_layer_pipe<NT, T, NOUT, HASB, OACT, Q + 1, AS>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us, act);
   } else {
     x3_step_pipe<NT, T, NOUT, Q, HASB, OACT, AS>(x3, p, hb, acc, lane, bias_last, hh, cs, isc, us, act);
   }
@@ -1384,111 +1236,6 @@ __device__ __forceinline__ float x3_squareplus_t(float x) {
   return 0.5f * (x + (CR ? x3_sqrt_cr(a) : __builtin_amdgcn_sqrtf(a)));
 }
 
-// Bin selection over a power-of-two number of bins N by halving (log2 N
-// compares, each followed by selects of the upper or lower half): bins
-// base..base+N-1 have left knots X / Y, raw widths Wd / heights Ht and knot
-// slope logits S (N + 1: both ends of every bin).  For strictly increasing
-// knots this is the last bin whose left knot is <= v (and bin 0 for v below
-// knot 1, or NaN): the same bin as the linear sweep of rqs_bin_monotone, with
-// 4 compares and 79 selects at K = 16 instead of 15 and 90.
-template <bool FWD, int N, int MX>
-__device__ __forceinline__ void x3_bsel(float v, const float (&X)[MX], const float (&Y)[MX], const float (&Wd)[N],
-                                        const float (&Ht)[N], const float (&S)[N + 1], float (&out)[6]) {
-  static_assert(MX >= N, "knot arrays cover the bins");
-  if constexpr (N == 1) {
-    out[0] = X[0]; out[1] = Y[0]; out[2] = Wd[0]; out[3] = Ht[0]; out[4] = S[0]; out[5] = S[1];
-  } else {
-    constexpr int H = N / 2;
-    const bool c = (FWD ? X[H] : Y[H]) <= v;
-    float X2[H], Y2[H], W2[H], H2[H], S2[H + 1];
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-      X2[i] = c ? X[H + i] : X[i];
-      Y2[i] = c ? Y[H + i] : Y[i];
-      W2[i] = c ? Wd[H + i] : Wd[i];
-      H2[i] = c ? Ht[H + i] : Ht[i];
-    }
-#pragma unroll
-    for (int i = 0; i <= H; ++i) S2[i] = c ? S[H + i] : S[i];
-    x3_bsel<FWD, H, H>(v, X2, Y2, W2, H2, S2, out);
-  }
-}
-
-// softmax_with_threshold's constants for a compile-time knot count (the
-// kernel's K equals the couplings' real K): c * rnorm * j as literals.
-template <int K>
-struct KnotLit {
-  static constexpr double c64 = 1e-5 / (1.0 - (double)K * 1e-5);
-  static constexpr float c = (float)c64;
-  static constexpr float norm = (float)(1.0 + c64 * (double)K);
-  static constexpr float rnorm = (float)(1.0 / (double)norm);
-  static constexpr float bc = c * rnorm;
-};
-
-// normalize_spline_params (utils.py:37-62) + the bin gather of
-// _compute_rqs_input (utils.py:205-232) for one (sample, dim) per lane, from
-// the raw logits P (widths P[0..K), heights P[K..2K), inner slopes
-// P[2K..3K-1)).  With s_j = 2 squareplus(logit_j) (the factor 1/2 cancels in
-// the quotient) and S = sum s_j, the normalised width is w_j = s_j a + bc
-// (a = rnorm / S, bc = c rnorm: one fma, as before) and knot j is
-// X_j = W_j a + j bc, W_j = s_0 + ... + s_{j-1} the raw running sum, which
-// the normalisation forms anyway (its last term is S): one fma per knot
-// instead of a normalising fma plus a running add.  The knots round
-// differently from the reference's cumsum of normalised widths in the last
-// ulp (as the fma'd widths already did); the spline is continuous across
-// knots.  KLIT: j bc as literals (the kernel's K is the couplings' K); else
-// from the runtime constants (padded knot counts).  Bin: x3_bsel; v at or
-// beyond the last knot gives the idx == K fill (NaN width, height and right
-// slope, utils.py:224-230) as rqs_bin_monotone.
-template <bool FWD, int K, bool CR, bool KLIT, int NPV>
-__device__ __forceinline__ RqsBin x3_bin(float v, const float (&P)[NPV], float krn, float kbc) {
-  float ws[K], hs[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    ws[j] = x3_squareplus2_t<CR>(P[j]);
-    hs[j] = x3_squareplus2_t<CR>(P[K + j]);
-  }
-  float X[K + 1], Y[K + 1];  // raw running sums, then knots
-  X[0] = 0.f;
-  Y[0] = 0.f;
-  X[1] = ws[0];
-  Y[1] = hs[0];
-#pragma unroll
-  for (int j = 1; j < K; ++j) {
-    X[j + 1] = X[j] + ws[j];
-    Y[j + 1] = Y[j] + hs[j];
-  }
-  const float rn = KLIT ? KnotLit<K>::rnorm : krn;
-  const float bc = KLIT ? KnotLit<K>::bc : kbc;
-  const float ax = rcp_refined(X[K]) * rn, ay = rcp_refined(Y[K]) * rn;
-#pragma unroll
-  for (int j = 1; j <= K; ++j) {
-    const float jb = KLIT ? (float)j * KnotLit<K>::bc : (float)j * bc;
-    X[j] = __builtin_fmaf(X[j], ax, jb);
-    Y[j] = __builtin_fmaf(Y[j], ay, jb);
-  }
-  float S[K + 1];
-  S[0] = 0.f;  // the boundary derivative 1 as the logit 0 (squareplus(0) == 1)
-  S[K] = 0.f;
-#pragma unroll
-  for (int j = 1; j < K; ++j) S[j] = P[2 * K + j - 1];
-  float o[6];
-  x3_bsel<FWD, K, K + 1>(v, X, Y, ws, hs, S, o);
-  RqsBin b;
-  const bool sliver = (FWD ? X[K] : Y[K]) <= v;
-  b.xk = sliver ? X[K] : o[0];
-  b.yk = sliver ? Y[K] : o[1];
-  b.w = sliver ? qnan() : __builtin_fmaf(o[2], ax, bc);
-  b.h = sliver ? qnan() : __builtin_fmaf(o[3], ay, bc);
-  const float lo = sliver ? 0.f : o[4];
-  const float hi = sliver ? qnan() : o[5];
-  b.dk = lo == 0.f ? 1.f : x3_squareplus_t<CR>(lo);
-  b.dkp1 = hi == 0.f ? 1.f : x3_squareplus_t<CR>(hi);
-  b.sk = b.h / b.w;
-  b.oob = (v < 0.f) || (v >= 1.f);
-  return b;
-}
-
 // Block: 4 waves x 32 samples, one 32-row input tile per weight group,
 // double-buffered in LDS.  Small parameters (BatchNorm, first Dense, biases,
 // ShiftBounds rows) are read from global memory (L2-resident), so the LDS
@@ -1568,12 +1315,12 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
   int nh, act, dt, kw1, kw_last;
   long long b0_rel, blast_rel;
   float krn, kcc = 0.f, kbc_res = 0.f;  // KnotConsts: rnorm; c (streaming) or c * rnorm as the pass carries it (RES)
-  bool padlast, klit;
+  bool padlast;
   if constexpr (LIT) {
     nh = 2; act = ZF_ACT_SWISH; dt = 2;
     kw1 = lit.kw1; kw_last = lit.kw_last;
     b0_rel = X3Lit::kB0; blast_rel = X3Lit::blast(K);
-    padlast = false; klit = true;
+    padlast = false;
     krn = lit.rnorm; kbc_res = lit.bc;
   } else {
     // (the fields in the order this function has always read them: another
@@ -1587,7 +1334,6 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
       krn = kc.rnorm; kcc = kc.c;
     }
     padlast = opc.kreal == K - 1;
-    klit = opc.kreal == K;  // x3_bin: the knot constants as literals
     b0_rel = opc.b_rel; blast_rel = opc.blast_rel;
     kw1 = opc.kw1;
   }
@@ -1612,9 +1358,6 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
   // this coupling's knots: a chain may mix knot counts up to the kernel's K
   // (x3_padded_knots); K - 1 real knots put the idx == K sliver at the
   // padded knot (rqs_bin_monotone padlast)
-#ifdef ZF_X3_MARK
-  klit = true;  // marker builds: count one x3_bin copy
-#endif
   // hidden biases are consecutive T x 32 blocks after Dense_0's (zf_flow.hip: b[l] = b[0] + l T 32)
   const long long b_rel = b0_rel + T * 32;
   floatx16 hb[T];
@@ -1627,20 +1370,14 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
   // layer scales and swishes them (act_swish) as it goes.
   // bf16x3 OACT: every tile's activation at the layer end (no switch inside
   // the group steps)
-#ifndef ZF_X3_EARLY
-#define ZF_X3_EARLY 1
-#endif
   // f16x2 swish at hidden 128 (one dim pair): scales from bounds (x3_early_scale)
-  constexpr bool kEarly = ZF_X3_EARLY && NT == 2 && !OACT && kPipe;
+  constexpr bool kEarly = NT == 2 && !OACT && kPipe;
   static_assert(!RES || kEarly, "the resident form runs the early-scale slot schedule only");
   // kEarly: the last layer's width / height tiles leave its last group
   // step as 2 squareplus (x3_step_slots_last SPT): K / 8 tiles of 16 per
   // lane half (one dim per half); ONE at K = 16: tile 0 (widths on half 0,
   // heights on half 1, the kSplitWH layout)
-#ifndef ZF_X3_PRESP
-#define ZF_X3_PRESP 1
-#endif
-  constexpr int kPreSP = (!ZF_X3_PRESP || !kEarly) ? 0 : !ONE ? K / 8 : (K == 16 ? 1 : 0);
+  constexpr int kPreSP = !kEarly ? 0 : !ONE ? K / 8 : (K == 16 ? 1 : 0);
   float umax = 0.f;
   x3_layer0<T, OACT, LIT>(opc, par, xs, rot, D, s, hh, lane, hb, NT == 2 ? 0 : (!OACT && (nh > 1 || kLastSW)) ? 1 : T,
                      kEarly ? &umax : nullptr);
@@ -1658,9 +1395,6 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
   // biases seed the accumulators.  f16x2: they seed them divided by the
   // unscale (exact: powers of two) and the accumulators are multiplied
   // by it afterwards (kSeedScaled).
-#ifndef ZF_X3_SEEDSCALED
-#define ZF_X3_SEEDSCALED 0
-#endif
   // f16x2 at hidden 128 (the slot schedule): zero-seeded accumulators and
   // one fma per value at the layer end (acc * us + bias) instead of a
   // bias * ius seed and an acc * us unscale (two multiplies per value)
@@ -1668,34 +1402,23 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
   // accumulation rounds at; sigmoid / softplus fold C colsum(W) into it,
   // 1e3-1e4 in the tiny-activation regime, where the zero-seeded sums of
   // the small centred terms plus one finish fma round far less)
-  constexpr bool kSeedScaled = NT == 2 && (ZF_X3_SEEDSCALED || !kPipe);
+  constexpr bool kSeedScaled = NT == 2 && !kPipe;
   // the hidden layers of a dim-pair flow (d8, d16: PAIRS, 2 waves per
   // SIMD) and of hidden-256 flows (cfg5: T = 8, one wave per SIMD) take
   // the f16x2 slot schedule too: only the last layer, which re-reads its
   // input once per pair, keeps the plain group steps (d8 -2.1%, cfg5
   // -3.4% kernel time)
-#ifndef ZF_X3_WIDE_PIPE
-#define ZF_X3_WIDE_PIPE 1
-#endif
-#ifndef ZF_X3_PAIRS_PIPE
-#define ZF_X3_PAIRS_PIPE 1
-#endif
-  constexpr bool kPipeH = kPipe || (ZF_X3_PAIRS_PIPE && (T == 4 || ZF_X3_WIDE_PIPE) && NT == 2 && !OACT);
+  constexpr bool kPipeH = kPipe || (NT == 2 && !OACT);
   // OACT with a narrowed activation set: the layer input's tiles 1..T-1
   // activated inside the group steps (x3_step_pipe AS), like the swish
-#ifndef ZF_X3_ACTIN
-#define ZF_X3_ACTIN 1
-#endif
   // (the centred set only: the five-way plain set spills 40 VGPRs that way, -13% on relu)
-  constexpr bool kActIn = ZF_X3_ACTIN && NT == 2 && ASET == 2 && kPipeH;
-  constexpr bool kSeedScaledH = NT == 2 && (ZF_X3_SEEDSCALED || !kPipeH);
+  constexpr bool kActIn = NT == 2 && ASET == 2 && kPipeH;
+  constexpr bool kSeedScaledH = NT == 2 && !kPipeH;
   // Three waves share a SIMD at hidden 128: the one streaming weight
   // groups (MFMAs) wins issue arbitration over one in its VALU-only
   // phases (layer 0, spline), so the matrix pipe idles less (+1.5% cfg2,
   // +1.2% d8; nothing to arbitrate at hidden 256, one wave per SIMD).
-#if ZF_X3_ABL != 4  // tuning ablation 4: no issue priority
   if constexpr (T == 4) __builtin_amdgcn_s_setprio(2);
-#endif
   X3TN(1);
   if constexpr (kEarly) {
     float eM = eU;  // max |v'| of the current layer input's pre-activations (exact from layer 2 on)
@@ -1737,10 +1460,8 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
     if constexpr (kPipeH) {
       typename XT<NT>::E cs[NT];
       splitk<NT, 0>(hb[0], cs);
-      halfx8 fs1[2];  // ZF_X3_FUSED: the k-step 1 terms carried between group steps
       x3_layer_pipe<NT, T, T, NT == 2 && !kSeedScaledH, OACT, 0, kActIn ? ASET : 0>(x3, pipe, hb, acc, lane, bh, hh,
-                                                                                 cs, isc, us,
-                                                             act, fs1);
+                                                                                 cs, isc, us, act);
     } else {
       x3_layer<NT, T, T, true, OACT>(x3, pipe, hb, acc, lane, bh, hh, isc, us, act);
     }
@@ -1781,13 +1502,10 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
     for (int o = 0; o < T; ++o)
       if (o == 0 || !kLastSW || (OACT && !(kActIn && kPipe))) x3_act_tile<NT, OACT, ASET>(hb[o], lisc, act);
   }
-#ifndef ZF_X3_PRESPLIT
-#define ZF_X3_PRESPLIT 1
-#endif
   // PAIRS at hidden 128 (f16x2): the last layer's input split once for
   // all pairs (d8 -1.0%; at hidden 256, one wave per SIMD, the per-pair
   // re-split hides in the MFMA gaps and the pre-split cost 5.6%)
-  constexpr bool kPre = ZF_X3_PRESPLIT && PAIRS && T == 4 && NT == 2 && !OACT;
+  constexpr bool kPre = PAIRS && T == 4 && NT == 2 && !OACT;
   halfx8 sp[kPre ? T : 1][2][2];
   if constexpr (kPre) {
 #pragma unroll
@@ -1816,9 +1534,8 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
     } else if constexpr (kPipe) {
       typename XT<NT>::E cs[NT];
       splitk<NT, 0>(hb[0], cs);
-      halfx8 fs1[2];
       x3_layer_pipe<NT, T, TL, !kSeedScaled, OACT, 0, kActIn ? ASET : 0>(x3, pipe, hb, pa, lane, bl, hh, cs, lisc,
-                                                                         lus, act, fs1);
+                                                                         lus, act);
     } else {
       x3_layer<NT, T, TL, kLastSW, OACT>(x3, pipe, hb, pa, lane, (kSeed || kSeedScaled) ? nullptr : bl, hh,
                                          lisc, lus, act);
@@ -1853,14 +1570,6 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
         }
       }
     X3M(11);
-#if ZF_X3_ABL == 10 || ZF_X3_ABL == 11  // tuning: 64 extra VALU (10: v_add, 11: v_exp) in the spline phase
-#pragma unroll
-    for (int q2 = 0; q2 < 64; ++q2) {
-      float dd;
-      if (ZF_X3_ABL == 10) asm volatile("v_add_f32 %0, %1, %2" : "=v"(dd) : "v"(pa[0][q2 & 15]), "v"(pa[1][q2 & 15]));
-      else asm volatile("v_exp_f32 %0, %1" : "=v"(dd) : "v"(pa[0][q2 & 15]));
-    }
-#endif
     // normalize_spline_params (utils.py:37-62) + RQ spline (utils.py:65-250)
     const int d = 2 * pr + hh;
     const bool dact = d < dt;  // the upper half idles on an odd last dim
@@ -1868,18 +1577,8 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
     {
       float* xp = xs + wrap((dact ? d : 0) + rot, D) * 32 + s;
       const float xv = *xp;
-#ifndef ZF_X3_BSEARCH
-#define ZF_X3_BSEARCH 0
-#endif
       RqsBin bin;
-      bool binned = false;
-      if constexpr (ZF_X3_BSEARCH && !kSplitWH && !kPreSP && (K == 8 || K == 16 || K == 32 || K == 64)) {
-        if (klit) {  // the halving search takes unpadded knots only, not yet squareplus'd ones
-          bin = x3_bin<!INV, K, OACT, true>(xv, P, krn, kbc());
-          binned = true;
-        }
-      }
-      if (!binned) {
+      {
         float w[K], hg[K];
         const float bc = kbc();
         if constexpr (kSplitWH) {
@@ -1920,12 +1619,9 @@ __device__ __forceinline__ void x3_nsc(const DevOp& op, const X3Sc& opc, const c
         float sl[K - 1];  // raw slope logits; the bin's two get squareplus'd
 #pragma unroll
         for (int j = 0; j < K - 1; ++j) sl[j] = P[2 * K + j];
-#ifndef ZF_X3_EXECBIN
-#define ZF_X3_EXECBIN 1
-#endif
         // the latch as exec-masked moves (rqs_bin_exec): -15% of the spline phase's VALU issue
         const auto spf = [](float v) { return v == 0.f ? 1.f : x3_squareplus_t<OACT>(v); };
-        if constexpr (ZF_X3_EXECBIN && K % 8 == 0) bin = rqs_bin_exec<!INV, K>(xv, w, hg, sl, spf, padlast);
+        if constexpr (K % 8 == 0) bin = rqs_bin_exec<!INV, K>(xv, w, hg, sl, spf, padlast);
         else bin = rqs_bin_monotone<!INV, K>(xv, w, hg, sl, spf, padlast);
         X3M(13);
       }

@@ -143,26 +143,18 @@ __global__ void lay_draw_kernel(float* __restrict__ s, int B, long long row0, in
 // gemm_x3_kernel's tile geometry (zf_train.hip) and its XCD-aware tile order
 constexpr int kX3BM = 128, kX3BN = 128, kX3BK = 32;
 constexpr int kX3RS = 40;              // halfs per LDS row (32 k + 8 pad = 80 B)
-// gemm_h2_kernel's LDS: ZF_H2_DB (default) double-buffers the k-tile stage
-// (one barrier per k-tile instead of two) in 64-B rows whose 16-B chunks are
-// XOR-swizzled by row bits 2-3 (16 lanes of a fragment read or a stage store
-// hit 16 distinct 4-bank groups; the 80-B padded rows of one buffer would
-// not leave room for two blocks per CU)
-#ifndef ZF_H2_DB
-#define ZF_H2_DB 1
-#endif
-constexpr bool kH2DB = ZF_H2_DB != 0;
-// resident blocks per CU the kernel is built and launched for (tuning: 3
-// needs the single-buffer stage's LDS and spills a few VGPRs)
-#ifndef ZF_H2_OCC
-#define ZF_H2_OCC 2
-#endif
-constexpr int kH2RS = kH2DB ? 32 : kX3RS;  // halfs per LDS row
-constexpr int kH2Pl = 128 * kH2RS;         // halfs per plane
-constexpr int kH2Buf = 4 * kH2Pl;          // one stage: A hi, A lo, B hi, B lo
-__device__ __forceinline__ int h2_off(int row, int chunk) {
-  return kH2DB ? row * 32 + 8 * (chunk ^ ((row >> 2) & 3)) : row * kX3RS + 8 * chunk;
-}
+// gemm_h2_kernel's LDS: the k-tile stage is double-buffered (one barrier per
+// k-tile instead of two) in 64-B rows whose 16-B chunks are XOR-swizzled by
+// row bits 2-3 (16 lanes of a fragment read or a stage store hit 16 distinct
+// 4-bank groups; the 80-B padded rows of one buffer would not leave room for
+// two blocks per CU)
+constexpr int kH2RS = 32;           // halfs per LDS row
+constexpr int kH2Pl = 128 * kH2RS;  // halfs per plane
+constexpr int kH2Buf = 4 * kH2Pl;   // one stage: A hi, A lo, B hi, B lo
+__device__ __forceinline__ int h2_off(int row, int chunk) { return row * 32 + 8 * (chunk ^ ((row >> 2) & 3)); }
+// resident blocks per CU the kernel is built and launched for (3 needs a
+// single-buffer stage's LDS and spills a few VGPRs)
+constexpr int kH2Occ = 2;
 typedef float tfloatx2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float sigmoidf(float z) { return 1.0f / (1.0f + expf(-z)); }
@@ -240,12 +232,12 @@ __device__ __forceinline__ float h2_act(int act, float v) {
 }
 
 template <bool WIDE, bool SW>
-__global__ __launch_bounds__(256, ZF_H2_OCC) void gemm_h2_kernel(int M, int N, int K, const float* __restrict__ A, int lda,
+__global__ __launch_bounds__(256, kH2Occ) void gemm_h2_kernel(int M, int N, int K, const float* __restrict__ A, int lda,
                                                       const _Float16* __restrict__ Wp, const unsigned* __restrict__ rin,
                                                       int kw, float* __restrict__ C, int ldc,
                                                       const float* __restrict__ bias, float* __restrict__ H,
                                                       unsigned* __restrict__ rout, int act) {
-  __shared__ __attribute__((aligned(16))) _Float16 lds[(kH2DB ? 2 : 1) * kH2Buf];
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * kH2Buf];
   __shared__ unsigned rowx[kX3BM];  // the tile's A-row maxima (float bits)
   __shared__ __attribute__((aligned(16))) float biasl[kX3BN];    // the tile's bias
   const int tid = threadIdx.x, lane = tid & 63;
@@ -371,7 +363,7 @@ __global__ __launch_bounds__(256, ZF_H2_OCC) void gemm_h2_kernel(int M, int N, i
   };
   auto kstep = [&](int it, int kk, Stage& S) __attribute__((always_inline)) {
     const int k0 = kk * kX3BK;
-    _Float16* const Ap = lds + (kH2DB ? (it & 1) * kH2Buf : 0);  // this k-tile's stage buffer
+    _Float16* const Ap = lds + (it & 1) * kH2Buf;  // this k-tile's stage buffer
     _Float16* const Bp = Ap + 2 * kH2Pl;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -416,10 +408,8 @@ __global__ __launch_bounds__(256, ZF_H2_OCC) void gemm_h2_kernel(int M, int N, i
           acc[i][j] = mf(0, 0, c);
         }
     }
-    // single buffer: the next store overwrites this stage; double buffer: the
-    // next store goes to the other one, which every wave finished reading
-    // before passing this k-tile's barrier
-    if (!kH2DB) __syncthreads();
+    // no barrier here: the next store goes to the other stage buffer, which
+    // every wave finished reading before passing this k-tile's barrier
   };
   int it = 0;
   for (int ti = 0; ti < mine; ++ti) {
@@ -434,7 +424,7 @@ __global__ __launch_bounds__(256, ZF_H2_OCC) void gemm_h2_kernel(int M, int N, i
       kstep(it, kk, S0);
       kstep(it + 1, kk + 1, S1);
     }
-    if (kH2DB) __syncthreads();  // the epilogue's LDS transpose spans both stage buffers
+    __syncthreads();  // the epilogue's LDS transpose spans both stage buffers
     epilogue();
   }
 }
@@ -449,7 +439,7 @@ int dense_gemm_h2(int M, int N, int K, const float* A, int lda, const void* Wp, 
   const long long ntiles = (long long)((N + kX3BN - 1) / kX3BN) * ((M + kX3BM - 1) / kX3BM);
   int dev = 0, ncu = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const dim3 grid((unsigned)std::min<long long>(ntiles, (long long)ZF_H2_OCC * ncu));
+  const dim3 grid((unsigned)std::min<long long>(ntiles, (long long)kH2Occ * ncu));
   const bool wide = N % 4 == 0 && ldc % 4 == 0 && (!C || al16(C)) && (!H || al16(H));
   const _Float16* W = static_cast<const _Float16*>(Wp);
   const bool sw = act == ZF_ACT_SWISH || !H;  // no activation stored: the swish-only form

@@ -226,20 +226,12 @@ __device__ __forceinline__ RqsBin rqs_bin_monotone(float v, const float (&w)[K],
 // the narrowed exec is carried between statements in an SGPR pair.  The
 // latched values are early-clobber: an input equal in value to one of them
 // (a zero slope logit and the zero lo seed) must not share its register.
-#ifndef ZF_CMPX_NOP
-#define ZF_CMPX_NOP 0
-#endif
-#if ZF_CMPX_NOP
-#define ZF_CMPX_PAD "s_nop 4\n\t"
-#else
-#define ZF_CMPX_PAD ""
-#endif
 #define ZF_KNOT_F(i)                                                                                   \
-  "v_add_f32 %[t], %[sx], %[sw]\n\tv_cmpx_le_f32 vcc, %[t], %[v]\n\t" ZF_CMPX_PAD "v_mov_b32 %[sx], %[t]\n\t"       \
+  "v_add_f32 %[t], %[sx], %[sw]\n\tv_cmpx_le_f32 vcc, %[t], %[v]\n\tv_mov_b32 %[sx], %[t]\n\t"       \
   "v_add_f32 %[sy], %[sy], %[sh]\n\tv_mov_b32 %[sw], %[w" #i "]\n\tv_mov_b32 %[sh], %[h" #i "]\n\t" \
   "v_mov_b32 %[lo], %[hi]\n\tv_mov_b32 %[hi], %[s" #i "]\n\t"
 #define ZF_KNOT_I(i)                                                                                   \
-  "v_add_f32 %[t], %[sy], %[sh]\n\tv_cmpx_le_f32 vcc, %[t], %[v]\n\t" ZF_CMPX_PAD "v_mov_b32 %[sy], %[t]\n\t"       \
+  "v_add_f32 %[t], %[sy], %[sh]\n\tv_cmpx_le_f32 vcc, %[t], %[v]\n\tv_mov_b32 %[sy], %[t]\n\t"       \
   "v_add_f32 %[sx], %[sx], %[sw]\n\tv_mov_b32 %[sw], %[w" #i "]\n\tv_mov_b32 %[sh], %[h" #i "]\n\t" \
   "v_mov_b32 %[lo], %[hi]\n\tv_mov_b32 %[hi], %[s" #i "]\n\t"
 #define ZF_KNOT_OPS(i) [w##i] "v"(w[i]), [h##i] "v"(h[i]), [s##i] "v"(s[i])
@@ -301,7 +293,7 @@ __device__ __forceinline__ RqsBin rqs_bin_exec(float v, const float (&w)[K], con
       (void)t;
     } else {
       asm("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\t"
-          "v_add_f32 %[t], %[a], %[da]\n\tv_cmpx_le_f32 vcc, %[t], %[v]\n\t" ZF_CMPX_PAD "v_mov_b32 %[a], %[t]\n\t"
+          "v_add_f32 %[t], %[a], %[da]\n\tv_cmpx_le_f32 vcc, %[t], %[v]\n\tv_mov_b32 %[a], %[t]\n\t"
           "v_add_f32 %[b], %[b], %[db]\n\t"
           "v_mov_b32 %[sw], %[nan]\n\tv_mov_b32 %[sh], %[nan]\n\tv_mov_b32 %[lo], 0\n\tv_mov_b32 %[hi], %[nan]\n\t"
           "s_mov_b64 exec, %[sv]"

@@ -2388,6 +2388,116 @@ int dp_combine(zf_trainer_t* t, double* roots, long long n, hipStream_t st) {
   return launch_tree_cols((const double*)t->d_gath, W, n, roots, st);
 }
 
+// ---- The coupling chain shared by the train-mode step (trainer_body) and the
+// eval-mode input gradients (trainer_vjp_chunk) ----
+
+// sp[i]: the state before op i; Roll is an index rotation, so it aliases its input.
+std::vector<float*> state_table(const zf_trainer_t* t) {
+  const zf_flow_desc& desc = t->desc;
+  std::vector<float*> sp(desc.n_ops + 1);
+  sp[0] = t->d_state;
+  for (int i = 0; i < desc.n_ops; ++i)
+    sp[i + 1] = desc.ops[i].kind == ZF_OP_ROLL ? sp[i] : t->d_state + (int64_t)(i + 1) * t->bmax * t->D;
+  return sp;
+}
+
+// The Dense chain of one coupling's conditioner: nb.Ubn -> Z[l], H[l] = act(Z[l]) -> nb.P
+// (dt * S raw spline parameters per row).  Bg: the batch that picks the GEMM form.
+int nsc_dense_fwd(zf_trainer_t* t, const zf_op_desc& op, zf_trainer::NscBufs& nb, long long Bg, int B, int DC,
+                  int out_last, hipStream_t st) {
+  const float* nat = t->d_nat;
+  const float* in = nb.Ubn;
+  int in_w = DC;
+  for (int l = 0; l <= op.n_hidden; ++l) {
+    const bool last = (l == op.n_hidden);
+    const int out_w = last ? out_last : op.hidden[l];
+    const int rc = gemm(false, Bg, B, out_w, in_w, in, in_w, nat + op.off_w[l], out_w, last ? nb.P : nb.Z[l], out_w, st,
+                        kEpiBias, nat + op.off_b[l], last ? nullptr : nb.H[l], nullptr, op.act,
+                        t->splitq ? t->d_split : nullptr, kSplitFloats);
+    if (rc) return rc;
+    if (!last) {
+      in = nb.H[l];
+      in_w = out_w;
+    }
+  }
+  return ZF_OK;
+}
+
+// The forward spline of B rows: one-wave blocks of 64 / dt rows, each row's dt * (3K - 1)
+// parameters staged in LDS.
+int spline_fwd_launch(const float* s_in, float* s_out, const float* P, float* ld, int B, int D, int dt, int K,
+                      int rot, hipStream_t st) {
+  const int rpb = kSplThreads / dt;
+  const size_t lds = (size_t)kSplThreads * (3 * K - 1) * sizeof(float);
+#define ZF_SPL(KTV)                                                                                          \
+  hipLaunchKernelGGL((spline_fwd_kernel<KTV>), dim3(blocks_for(B, rpb)), dim3(kSplThreads), lds, st, s_in, \
+                     s_out, P, ld, B, D, dt, K, rot)
+  ZF_KNOT_DISPATCH(K, ZF_SPL);
+#undef ZF_SPL
+  ZF_CHECK_LAUNCH("spline_fwd_kernel");
+  return ZF_OK;
+}
+
+// Its reverse: g_out -> g_in (transformed columns) and gP.  d loss / d log_det is gl for
+// every row, or (ROWGL) row b's is glr[b].
+template <bool ROWGL>
+int spline_bwd_launch(const float* s_in, const float* P, const float* g_out, float gl, float* g_in, float* gP, int B,
+                      int D, int dt, int K, int rot, const float* glr, hipStream_t st) {
+  const int rpb = kSplThreads / dt;
+  const size_t lds = (size_t)kSplThreads * (3 * K - 1) * sizeof(float);
+#define ZF_SPL(KTV)                                                                                                 \
+  hipLaunchKernelGGL((spline_bwd_kernel<KTV, ROWGL>), dim3(blocks_for(B, rpb)), dim3(kSplThreads), lds, st, s_in, \
+                     P, g_out, gl, g_in, gP, B, D, dt, K, rot, glr)
+  ZF_KNOT_DISPATCH(K, ZF_SPL);
+#undef ZF_SPL
+  ZF_CHECK_LAUNCH(ROWGL ? "spline_bwd_kernel<rowgl>" : "spline_bwd_kernel");
+  return ZF_OK;
+}
+
+// The input gradients of one coupling's Dense chain, last layer first.  gout
+// (out_w wide) is d loss / d (layer l's output); layer l's GEMM writes
+// d loss / d (its input) to gin(l): nb.gU for layer 0, else nb.gA / nb.gB in turn.
+struct DgradChain {
+  zf_trainer_t* t;
+  const zf_op_desc& op;
+  zf_trainer::NscBufs& nb;
+  int DC;
+  const float* gout;
+  int out_w;
+  int which = 0;
+  int in_w(int l) const { return l == 0 ? DC : op.hidden[l - 1]; }
+  float* gin(int l) const { return l == 0 ? nb.gU : (which ? nb.gB : nb.gA); }
+  // g_in = gout . W_l^T (through the activation of layer l-1 when l > 0), then on to layer l-1
+  int layer(int l, long long Bg, int B, hipStream_t st) {
+    float* const g = gin(l);
+    const int w = in_w(l);
+    const int rc = gemm(true, Bg, B, w, out_w, gout, out_w, t->d_nat + op.off_w[l], out_w, g, w, st,
+                        l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? nb.Z[l - 1] : nullptr, op.act,
+                        t->splitq ? t->d_split : nullptr, kSplitFloats);
+    if (rc) return rc;
+    if (l > 0) {
+      gout = g;
+      out_w = w;
+      which ^= 1;
+    }
+    return ZF_OK;
+  }
+};
+
+// The latent's constants (latent_loss_kernel, latent_vjp_kernel): the Beta
+// log-normaliser and the log mass of the truncated Normal.
+struct LatentConsts {
+  int lt;
+  float a, betac, tnm;
+  explicit LatentConsts(const zf_flow_desc& desc)
+      : lt(desc.latent),
+        a((float)desc.latent_param),
+        betac(desc.latent == ZF_LATENT_BETA
+                  ? (float)(-(std::lgamma(desc.latent_param) * 2.0 - std::lgamma(2.0 * desc.latent_param)))
+                  : 0.f),
+        tnm((float)std::log1p(-2.0 * 0.5 * std::erfc(5.0 / std::sqrt(2.0)))) {}
+};
+
 // Train-mode forward + loss + reverse pass from the staged batch of B rows
 // (this rank's shard of a global batch of Bg rows); the loss lands in
 // loss_slot(t), the gradient in G (natural blob layout, fp32).
@@ -2405,11 +2515,7 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
   const zf_flow_desc& desc = t->desc;
   float* nat = t->d_nat;
   double* G64 = t->d_g64;
-  // state before op i; Roll is an index rotation, so it aliases its input
-  std::vector<float*> sp(desc.n_ops + 1);
-  sp[0] = t->d_state;
-  for (int i = 0; i < desc.n_ops; ++i)
-    sp[i + 1] = desc.ops[i].kind == ZF_OP_ROLL ? sp[i] : t->d_state + (int64_t)(i + 1) * t->bmax * D;
+  const std::vector<float*> sp = state_table(t);
   auto state = [&](int i) { return sp[i]; };
   // a leading ShiftBounds sets ld itself (sb_forward_kernel, first)
   if (desc.n_ops == 0 || desc.ops[0].kind != ZF_OP_SHIFT_BOUNDS)
@@ -2471,40 +2577,15 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
                            nb.mean, nb.rstd, bn + 2 * DC, bn + 3 * DC, nb.Uhat, nb.Ubn, B, DC);
         ZF_CHECK_LAUNCH("bn_apply_kernel");
       }
-      const float* in = nb.Ubn;
-      int in_w = DC;
-      for (int l = 0; l <= op.n_hidden; ++l) {
-        const bool last = (l == op.n_hidden);
-        const int out_w = last ? dt * S : op.hidden[l];
-        float* Z = last ? nb.P : nb.Z[l];
-        rc = zf::gemm(false, Bg, B, out_w, in_w, in, in_w, nat + op.off_w[l], out_w, Z, out_w, st, zf::kEpiBias,
-                      nat + op.off_b[l], last ? nullptr : nb.H[l], nullptr, op.act, t->splitq ? t->d_split : nullptr,
-                      zf::kSplitFloats);
-        if (rc) return rc;
-        if (!last) {
-          in = nb.H[l];
-          in_w = out_w;
-        }
-      }
-      const int rpb = zf::kSplThreads / dt;
-#define ZF_SPL(KTV) hipLaunchKernelGGL((zf::spline_fwd_kernel<KTV>), dim3(zf::blocks_for(B, rpb)), dim3(zf::kSplThreads),\
-                         (size_t)zf::kSplThreads * S * sizeof(float), st, sin, sout, nb.P,\
-                         t->d_ld, B, D, dt, op.knots, rot)
-      ZF_KNOT_DISPATCH(op.knots, ZF_SPL);
-#undef ZF_SPL
-      ZF_CHECK_LAUNCH("spline_fwd_kernel");
+      if ((rc = nsc_dense_fwd(t, op, nb, Bg, B, DC, dt * S, st))) return rc;
+      if ((rc = spline_fwd_launch(sin, sout, nb.P, t->d_ld, B, D, dt, op.knots, rot, st))) return rc;
     } else {
       return zf::einval("op %d: unknown kind", i);
     }
   }
   rots[desc.n_ops] = rot;
   // ---- latent + loss ----
-  const int lt = desc.latent;
-  const float a = (float)desc.latent_param;
-  const float betac = lt == ZF_LATENT_BETA
-                          ? (float)(-(std::lgamma(desc.latent_param) * 2.0 - std::lgamma(2.0 * desc.latent_param)))
-                          : 0.f;
-  const float tnm = (float)std::log1p(-2.0 * 0.5 * std::erfc(5.0 / std::sqrt(2.0)));
+  const LatentConsts lc(desc);
   float* g = t->d_g0;
   float* g_prev = t->d_g1;
   {
@@ -2512,7 +2593,7 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
     // leaves that tile the 256-row blocks are summed inside the loss kernel
     const bool fused = ll.rows > 0 && ll.rows <= 256 && 256 % ll.rows == 0;
     hipLaunchKernelGGL(zf::latent_loss_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, state(desc.n_ops),
-                       t->d_ld, B, Bg, D, rot, lt, a, betac, tnm, g, t->d_rowloss, fused ? ll.rows : 0, ll.n,
+                       t->d_ld, B, Bg, D, rot, lc.lt, lc.a, lc.betac, lc.tnm, g, t->d_rowloss, fused ? ll.rows : 0, ll.n,
                        t->d_leaf);
     ZF_CHECK_LAUNCH("latent_loss_kernel");
     if (!fused) {
@@ -2542,40 +2623,21 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
     zf_trainer::NscBufs& nb = t->nsc[i];
     const int r = rots[i];
     // spline: g -> g_prev (transformed columns), gP
-    const int rpb = zf::kSplThreads / dt;
-#define ZF_SPL(KTV) hipLaunchKernelGGL((zf::spline_bwd_kernel<KTV>), dim3(zf::blocks_for(B, rpb)), dim3(zf::kSplThreads),\
-                       (size_t)zf::kSplThreads * S * sizeof(float), st, state(i), nb.P, g, gl,\
-                       g_prev, nb.gP, B, D, dt, op.knots, r)
-    ZF_KNOT_DISPATCH(op.knots, ZF_SPL);
-#undef ZF_SPL
-    ZF_CHECK_LAUNCH("spline_bwd_kernel");
+    rc = spline_bwd_launch<false>(state(i), nb.P, g, gl, g_prev, nb.gP, B, D, dt, op.knots, r, nullptr, st);
+    if (rc) return rc;
     // MLP reverse
-    const float* gout = nb.gP;
-    int out_w = dt * S;
-    float* gbufs[2] = {nb.gA, nb.gB};
-    int which = 0;
+    DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
     for (int l = op.n_hidden; l >= 0; --l) {
-      const int in_w = l == 0 ? DC : op.hidden[l - 1];
+      const int in_w = dg.in_w(l);
       const float* hin = l == 0 ? nb.Ubn : nb.H[l - 1];
       // dW_l = hin^T . gout ; db_l = colsum(gout): leaves capped by the
       // split-K workspace (a power of two, the same on every rank)
-      const int cap = pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * out_w))));
-      rc = zf::wgrad_deferred(wq, in_w, out_w, B, leaves_for(B, Bg, W, cap), hin, gout, G64 + op.off_w[l],
+      const int cap = pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * dg.out_w))));
+      rc = zf::wgrad_deferred(wq, in_w, dg.out_w, B, leaves_for(B, Bg, W, cap), hin, dg.gout, G64 + op.off_w[l],
                               G64 + op.off_b[l], t->d_ws, t->d_ws2, st);
       if (rc) return rc;
-      // g_in = gout . W_l^T
-      float* gin = l == 0 ? nb.gU : gbufs[which];
-      if ((rc = zf::wgrad_before_write(wq, gin, st))) return rc;  // a deferred dW GEMM still reads it
-      // (through swish of layer l-1 when l > 0)
-      rc = zf::gemm(true, Bg, B, in_w, out_w, gout, out_w, nat + op.off_w[l], out_w, gin, in_w, st,
-                    l > 0 ? zf::kEpiDSwish : zf::kEpiNone, nullptr, nullptr, l > 0 ? nb.Z[l - 1] : nullptr, op.act,
-                    t->splitq ? t->d_split : nullptr, zf::kSplitFloats);
-      if (rc) return rc;
-      if (l > 0) {
-        gout = gin;
-        out_w = in_w;
-        which ^= 1;
-      }
+      if ((rc = zf::wgrad_before_write(wq, dg.gin(l), st))) return rc;  // a deferred dW GEMM still reads it
+      if ((rc = dg.layer(l, Bg, B, st))) return rc;
     }
     // BatchNorm: gU holds d loss / d Ubn
     float* bn = nat + op.off_bn;
@@ -2669,10 +2731,7 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
   float* nat = t->d_nat;
-  std::vector<float*> sp(desc.n_ops + 1);
-  sp[0] = t->d_state;
-  for (int i = 0; i < desc.n_ops; ++i)
-    sp[i + 1] = desc.ops[i].kind == ZF_OP_ROLL ? sp[i] : t->d_state + (int64_t)(i + 1) * t->bmax * D;
+  const std::vector<float*> sp = state_table(t);
   const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
   if (!sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
   // ---- forward (eval mode) ----
@@ -2696,41 +2755,18 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
       hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
                          (const float*)(nat + op.off_bn), nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
       ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
-      const float* in = nb.Ubn;
-      int in_w = DC;
-      for (int l = 0; l <= op.n_hidden; ++l) {
-        const bool last = (l == op.n_hidden);
-        const int out_w = last ? dt * S : op.hidden[l];
-        rc = gemm(false, B, B, out_w, in_w, in, in_w, nat + op.off_w[l], out_w, last ? nb.P : nb.Z[l], out_w, st,
-                  kEpiBias, nat + op.off_b[l], last ? nullptr : nb.H[l], nullptr, op.act,
-                  t->splitq ? t->d_split : nullptr, kSplitFloats);
-        if (rc) return rc;
-        if (!last) {
-          in = nb.H[l];
-          in_w = out_w;
-        }
-      }
-      const int rpb = kSplThreads / dt;
-#define ZF_SPL(KTV) hipLaunchKernelGGL((spline_fwd_kernel<KTV>), dim3(blocks_for(B, rpb)), dim3(kSplThreads),\
-                         (size_t)kSplThreads * S * sizeof(float), st, sin, sout, nb.P, t->d_ld, B, D, dt, op.knots, rot)
-      ZF_KNOT_DISPATCH(op.knots, ZF_SPL);
-#undef ZF_SPL
-      ZF_CHECK_LAUNCH("spline_fwd_kernel");
+      if ((rc = nsc_dense_fwd(t, op, nb, B, B, DC, dt * S, st))) return rc;
+      if ((rc = spline_fwd_launch(sin, sout, nb.P, t->d_ld, B, D, dt, op.knots, rot, st))) return rc;
     } else {
       return einval("op %d: unknown kind", i);
     }
   }
   // ---- latent, log_prob, the per-row cotangent ----
-  const int lt = desc.latent;
-  const float a = (float)desc.latent_param;
-  const float betac = lt == ZF_LATENT_BETA
-                          ? (float)(-(std::lgamma(desc.latent_param) * 2.0 - std::lgamma(2.0 * desc.latent_param)))
-                          : 0.f;
-  const float tnm = (float)std::log1p(-2.0 * 0.5 * std::erfc(5.0 / std::sqrt(2.0)));
+  const LatentConsts lc(desc);
   float* g = t->d_g0;
   float* g_prev = t->d_g1;
   hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, cot, B, D, rot,
-                     lt, a, betac, tnm, lp_out, t->d_ce, g);
+                     lc.lt, lc.a, lc.betac, lc.tnm, lp_out, t->d_ce, g);
   ZF_CHECK_LAUNCH("latent_vjp_kernel");
   if (!gx && !gc) return ZF_OK;
   // ---- reverse ----
@@ -2742,30 +2778,11 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
     nsc_dims(t, op, dt, dc, DC, S);
     zf_trainer::NscBufs& nb = t->nsc[i];
     const int r = rots[i];
-    const int rpb = kSplThreads / dt;
-#define ZF_SPL(KTV) hipLaunchKernelGGL((spline_bwd_kernel<KTV, true>), dim3(blocks_for(B, rpb)), dim3(kSplThreads),\
-                       (size_t)kSplThreads * S * sizeof(float), st, sp[i], nb.P, g, 0.f, g_prev, nb.gP, B, D, dt,\
-                       op.knots, r, (const float*)t->d_ce)
-    ZF_KNOT_DISPATCH(op.knots, ZF_SPL);
-#undef ZF_SPL
-    ZF_CHECK_LAUNCH("spline_bwd_kernel<rowgl>");
-    const float* gout = nb.gP;
-    int out_w = dt * S;
-    float* gbufs[2] = {nb.gA, nb.gB};
-    int which = 0;
-    for (int l = op.n_hidden; l >= 0; --l) {
-      const int in_w = l == 0 ? DC : op.hidden[l - 1];
-      float* gin = l == 0 ? nb.gU : gbufs[which];
-      rc = gemm(true, B, B, in_w, out_w, gout, out_w, nat + op.off_w[l], out_w, gin, in_w, st,
-                l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? nb.Z[l - 1] : nullptr, op.act,
-                t->splitq ? t->d_split : nullptr, kSplitFloats);
-      if (rc) return rc;
-      if (l > 0) {
-        gout = gin;
-        out_w = in_w;
-        which ^= 1;
-      }
-    }
+    rc = spline_bwd_launch<true>(sp[i], nb.P, g, 0.f, g_prev, nb.gP, B, D, dt, op.knots, r, t->d_ce, st);
+    if (rc) return rc;
+    DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
+    for (int l = op.n_hidden; l >= 0; --l)
+      if ((rc = dg.layer(l, B, B, st))) return rc;
     const float* bn = nat + op.off_bn;
     hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
                        bn + 2 * DC, (const float*)nb.rstd, (const float*)t->d_ce, g_prev, gc, gc_assign, B, D, C, dt,
@@ -3190,20 +3207,12 @@ int spline_rows(bool inverse, const float* s_in, float* s_out, const float* P, f
   // the layered eval path takes up to 200 knots (the block's rows of 3K - 1
   // parameters staged in LDS: 64 x 599 floats); training stays at kMaxK
   if (dt < 1 || dt > kSplThreads || K < 1 || K > 200) return enotsup("spline rows: transformed dims or knots out of range");
+  if (!inverse) return spline_fwd_launch(s_in, s_out, P, ld, B, D, dt, K, rot, st);
   const int S = 3 * K - 1, rpb = kSplThreads / dt;
   const size_t lds = (size_t)kSplThreads * S * sizeof(float);
-  if (inverse) {
-    hipLaunchKernelGGL(spline_inv_kernel, dim3(blocks_for(B, rpb)), dim3(kSplThreads), lds, st, s_in, s_out, P, B,
-                       D, dt, K, rot);
-    ZF_CHECK_LAUNCH("spline_inv_kernel");
-    return ZF_OK;
-  }
-#define ZF_SPL(KTV)                                                                                          \
-  hipLaunchKernelGGL((spline_fwd_kernel<KTV>), dim3(blocks_for(B, rpb)), dim3(kSplThreads), lds, st, s_in, \
-                     s_out, P, ld, B, D, dt, K, rot)
-  ZF_KNOT_DISPATCH(K, ZF_SPL);
-#undef ZF_SPL
-  ZF_CHECK_LAUNCH("spline_fwd_kernel");
+  hipLaunchKernelGGL(spline_inv_kernel, dim3(blocks_for(B, rpb)), dim3(kSplThreads), lds, st, s_in, s_out, P, B,
+                     D, dt, K, rot);
+  ZF_CHECK_LAUNCH("spline_inv_kernel");
   return ZF_OK;
 }
 
