@@ -6,7 +6,7 @@ JAX).  This module restates that train-mode loss function by function after
 ``oracle/zf_oracle.py`` (the NumPy oracle pinned by the reference's KATs) in
 PyTorch ops, so that reverse-mode autograd in float64 yields the exact
 gradient of the same arithmetic — the yardstick for the GPU trainer's
-hand-written reverse kernels (``zf_train.hip``), compared per parameter in
+hand-written reverse kernels (``zf_train.hip`` and the headers it includes), compared per parameter in
 ``tests/test_gpu_train.py``.  ``tests/test_oracle_torch.py`` checks that this
 restatement's forward equals the NumPy oracle's (fp64, 1e-12).
 

@@ -142,7 +142,7 @@ FAULTS = ("schedule_at_count_plus_1", "clip_below_max_norm", "norm_over_statisti
 
 def chain_kernel_f32(theta, g, slots, count, chain, mask, decay_mask=None, fault=None):
     """sumsq_leaf_kernel + opt_prologue_kernel + chain_update_kernel of
-    zf_train.hip operation by operation: the scalars (norm, clip factor,
+    zf_optim.hip operation by operation: the scalars (norm, clip factor,
     learning rate, bias corrections) formed in double and stored as float,
     the stages in float32.  The generic stage loop and the specialised forms
     share their stage functions, so this is the arithmetic of every form.

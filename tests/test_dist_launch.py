@@ -120,7 +120,7 @@ def test_trainer_reduction_schedule_rank_invariant(tmp_path, world, rows):
     """The trainer's batch-reduction schedule (leaves of ~32 rows whose count
     depends on the global batch only, a pairwise fp64 tree, ranks combining
     their subtree roots by the top of the tree; zenflow_amd.dist mirrors
-    zf_train.hip's leaves_for / tree_n): `world` ranks produce bit for bit the
+    zf_reduce.h's leaves_for / tree_n): `world` ranks produce bit for bit the
     one-device sum of the whole batch, on every rank."""
     from zenflow_amd.dist import leaf_tree_colsum, reduction_leaves
     from zenflow_amd.launch import spawn

@@ -1,5 +1,5 @@
 """Optimiser chains on the device (zenflow_amd/optim.py; sumsq_leaf_kernel,
-opt_prologue_kernel and chain_update_kernel of zf_train.hip) against the
+opt_prologue_kernel and chain_update_kernel of zf_optim.hip) against the
 float64 reference of tests/optim_ref.py, teacher forced as
 tests/test_gpu_train_trajectory.py::test_teacher_forced_trajectory: 12 steps
 over ``train_ref.trajectory_batches()`` on the 256-row cases, the handle

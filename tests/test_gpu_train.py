@@ -337,7 +337,7 @@ def test_step_graph_cache_eviction(monkeypatch):
 def test_split_set_gemm_matches_single_kernel(name, N, seed, monkeypatch):
     """Small batches run the 64x64 GEMM tiles as four blocks, one per
     accumulator set of the interleaved kernel, plus a combine (SPLITQ in
-    zf_train.hip): the same loss, gradient and trained parameters, bit for
+    zf_gemm.h): the same loss, gradient and trained parameters, bit for
     bit, as the single-kernel form (ZF_TRAIN_SPLITQ=0).  At 65536 rows the
     first Dense runs one thread per output under either setting (ADVICE r4:
     the switch names the small-batch forms only)."""

@@ -16,7 +16,7 @@ on the entries a mask selects (the parameters of a blob that also holds the
 batch statistics).
 
 ``adam_tolerance`` bounds what an fp32 evaluation of that update
-(adam_kernel in zf_train.hip) may differ by, per element:
+(adam_kernel in zf_train_kernels.h) may differ by, per element:
 
     2^-23 |theta_ref| + lr (t + 8) 2^-23 (Ahat / (sqrt(vhat) + eps) + wd |theta_t|)
 
@@ -141,7 +141,7 @@ FAULTS = ("nesterov_b1t", "count_by_2", "m_not_carried", "decay_on_stepped")
 
 
 def adam_kernel_f32(theta, g, m, v, t, opt, fault=None):
-    """adam_kernel + step_update of zf_train.hip operation by operation in
+    """adam_kernel + step_update of zf_train_kernels.h operation by operation in
     float32 (bias corrections formed in double and stored as float, as there):
     ``(theta_next, m, v)``.  ``fault``: one of FAULTS, a deliberately wrong
     variant for tests/test_train_ref_host.py."""

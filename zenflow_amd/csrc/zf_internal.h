@@ -41,10 +41,16 @@ inline int enotsup(const char* msg) {
     if (_zf_rc != ZF_OK) return _zf_rc;                    \
   } while (0)
 
-// Post-launch check: a bad launch configuration surfaces here.
-#define ZF_CHECK_LAUNCH(name) ZF_TRY_HIP(hipGetLastError())
+// Post-launch check: a bad launch configuration surfaces here, recorded
+// under the kernel's name.
+#define ZF_CHECK_LAUNCH(name)                                     \
+  do {                                                            \
+    int _zf_rc = ::zf::hip_status(hipGetLastError(), (name));     \
+    if (_zf_rc != ZF_OK) return _zf_rc;                           \
+  } while (0)
 
-// Trainer pieces the layered eval path (zf_layered.hip) runs (zf_train.hip):
+// Trainer pieces the layered eval path (zf_layered.hip) runs, defined in
+// zf_train.hip over zf_gemm.h (gemm) and zf_train_spline.h (spline_rows_launch):
 // C = A . W + bias (W row-major [K][N], a FLAX Dense kernel) and, when H is
 // given, H = act(C) (the trainer's fused epilogue).  Mg: the batch that
 // picks the tile shape.  rmax (optional): max |output row| as float bits

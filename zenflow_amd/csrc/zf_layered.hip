@@ -24,6 +24,7 @@
 // A handle's workspace is its own: calls on one handle are serialised by the
 // caller (as every zf_flow_* call on one stream is).
 #include "zf_flow_dev.h"
+#include "zf_x3_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -140,10 +141,8 @@ __global__ void lay_draw_kernel(float* __restrict__ s, int B, long long row0, in
   s[i] = latent_draw(lt, param, seed, row0 + b, d);
 }
 
-// gemm_x3_kernel's tile geometry (zf_train.hip) and its XCD-aware tile order
-constexpr int kX3BM = 128, kX3BN = 128, kX3BK = 32;
-constexpr int kX3RS = 40;              // halfs per LDS row (32 k + 8 pad = 80 B)
-// gemm_h2_kernel's LDS: the k-tile stage is double-buffered (one barrier per
+// gemm_h2_kernel runs gemm_x3_kernel's tile geometry, XCD-aware tile order and
+// sigmoid (zf_x3_tile.h).  Its LDS: the k-tile stage is double-buffered (one barrier per
 // k-tile instead of two) in 64-B rows whose 16-B chunks are XOR-swizzled by
 // row bits 2-3 (16 lanes of a fragment read or a stage store hit 16 distinct
 // 4-bank groups; the 80-B padded rows of one buffer would not leave room for
@@ -156,14 +155,6 @@ __device__ __forceinline__ int h2_off(int row, int chunk) { return row * 32 + 8 
 // single-buffer stage's LDS and spills a few VGPRs)
 constexpr int kH2Occ = 2;
 typedef float tfloatx2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float sigmoidf(float z) { return 1.0f / (1.0f + expf(-z)); }
-
-__device__ __forceinline__ int x3_tile(int ti, int ntiles) {
-  const int b = blockIdx.x, G = gridDim.x;
-  if ((G & 7) == 0 && ntiles % G == 0) return ti * G + (b & 7) * (G >> 3) + (b >> 3);
-  return b + ti * G;
-}
 
 // ---- Eval-only Dense layers on f16x2 split MFMA (the layered path) ----------
 // C / H = act(A . W + bias) for the layered eval path's Dense layers after

@@ -37,7 +37,7 @@ int optim_chain_step(float* prm, const float* g, const unsigned char* mask, cons
                      const ChainArgs& a, int form, bool clip, float max_norm, bool has_lr, const zf_schedule& sched,
                      bool has_adam, float b1, float b2, OptScalars* sc, double* leaf, int n_leaves, hipStream_t st);
 
-// The (n)adamw step counter bc[4] of zf_train.hip as `count` steps leave it.
+// The (n)adamw step counter bc[4] (step_update, zf_train_kernels.h) as `count` steps leave it.
 int optim_set_count(float* bc, int count, float b1, float b2);
 
 }  // namespace zf

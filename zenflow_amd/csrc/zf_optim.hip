@@ -7,14 +7,15 @@
 //                        bias corrections, count += 1 (the device scalars)
 //   chain_update_kernel  one pass over the blob: the stages in registers
 // The same three launches in the captured step graph and eagerly.  A
-// translation unit of its own: the trainer's kernels (zf_train.hip) stay the
-// code object they were.
+// translation unit of its own: the trainer's kernels (zf_train.hip and the
+// headers it includes) stay the code object they were.
 #include "zf_optim.h"
 
 namespace zf {
 namespace {
 
-// The pairwise tree of zf_train.hip's lds_tree over 256 LDS doubles, all
+// The pairwise tree of zf_reduce.h's lds_tree over 256 LDS doubles (restated:
+// this unit must not include a header that defines kernels), all
 // threads of the 256-thread block taking part: level s adds element i + s
 // into i for i a multiple of 2s.  Result in p[0].
 __device__ __forceinline__ void block_tree_256(double* p) {
@@ -25,7 +26,7 @@ __device__ __forceinline__ void block_tree_256(double* p) {
   }
 }
 
-// The (n)adamw counter of zf_train.hip (step_update there): bc[0] = step t
+// The (n)adamw counter of zf_train_kernels.h (step_update there): bc[0] = step t
 // as int bits, bc[1] = 1 - b1^t, bc[2] = 1 - b1^(t+1), bc[3] = 1 - b2^t, the
 // same expressions so that a restored counter has the bits a run reaches.
 __global__ void set_count_kernel(float* __restrict__ bc, int count, float b1, float b2) {

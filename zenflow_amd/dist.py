@@ -117,7 +117,7 @@ class HostAllgather:
 
 def reduction_leaves(rows: int, global_rows: int, world: int, cap: int = 4096) -> Tuple[int, int]:
     """(leaves on this rank, rows per leaf) of every batch reduction of the
-    trainer — the host mirror of zf_train.hip ``leaves_for``: ~32 rows per
+    trainer — the host mirror of zf_reduce.h ``leaves_for``: ~32 rows per
     leaf, at most ``cap`` (a power of two) leaves in the global batch, a
     power of two per rank."""
     want = max(1, min(int(global_rows) // 32, int(cap)))
@@ -127,7 +127,7 @@ def reduction_leaves(rows: int, global_rows: int, world: int, cap: int = 4096) -
 
 
 def tree_sum(leaves: np.ndarray) -> np.ndarray:
-    """The trainer's pairwise leaf tree (zf_train.hip ``tree_n``) in fp64 over
+    """The trainer's pairwise leaf tree (zf_reduce.h ``tree_n``) in fp64 over
     axis 0: level s adds element i + s into i for i a multiple of 2s."""
     v = [np.asarray(x, np.float64) for x in leaves]
     n = len(v)

@@ -84,7 +84,7 @@ __all__ = [
 # ---- schedules -------------------------------------------------------------------
 def _segment_value(kind: int, p: Sequence[float], c: float) -> float:
     """One segment at c = count - boundary, operation by operation as
-    sched_segment in zf_train.hip."""
+    sched_segment in zf_optim.hip."""
     if kind == L.ZF_SCHED_LINEAR:
         init, end, steps, begin = p[0], p[1], p[2], p[3]
         if steps <= 0.0:
