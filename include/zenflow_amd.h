@@ -368,6 +368,38 @@ int zf_trainer_loss_grad_cond_shard(zf_trainer_t* trainer, const float* x, const
 int zf_trainer_step_cond_shard(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows,
                                int64_t global_rows, double* loss, float* gc, void* stream);
 
+/* Weighted maximum likelihood.  With the reference the loss is user-visible
+ * JAX, and a user with weighted samples (Monte-Carlo event weights, sWeights,
+ * importance weights, class-balance weights) writes
+ *   -(w * lp).sum() / w.sum()
+ * around flow.apply(..., train=True).  Here: w (device, this rank's `rows`
+ * weights, fp32) gives
+ *   loss = -sum_b w_b lp_b / Wsum,   Wsum = sum_b w_b over the global batch,
+ * lp_b the train-mode log_prob after nan_to_num, as in the entries above.
+ *   - The weights enter at the loss only.  BatchNorm's batch mean / variance,
+ *     ShiftBounds' batch min / max and the running-statistics updates are taken
+ *     over all rows, zero-weight rows included (what the reference computes for
+ *     the loss above): the statistics after an update_stats pass have the bits
+ *     of the unweighted pass, and a zero-weight row still has a non-zero
+ *     d loss / d c through the batch statistics.
+ *   - Row b's cotangent is -w_b / Wsum where lp_b is finite before nan_to_num
+ *     and 0 elsewhere; Wsum is an fp64 sum over the loss's own leaf tree, so
+ *     every rank gets the same bits, and equal power-of-two shards the bits of
+ *     one device.  Scaling every weight by a power of two changes no bit.
+ *   - Weights may be zero or negative; Wsum must be positive.  That is not
+ *     checked here: a non-positive sum gives a non-finite loss.  No index is
+ *     derived from a weight.
+ *   - loss[0] is the weighted mean as is (fp64).
+ * gc as in the _cond_ entries (may be NULL).  w == NULL: exactly the _cond_
+ * entries.  The weighted step replays a captured graph of its own per batch
+ * size (weighted and unweighted steps may alternate on one trainer); with gc
+ * it launches the kernels eagerly. */
+int zf_trainer_loss_grad_weighted_shard(zf_trainer_t* trainer, const float* x, const float* c, const float* w,
+                                        int64_t rows, int64_t global_rows, int update_stats, double* loss,
+                                        float* grad, float* gc, void* stream);
+int zf_trainer_step_weighted_shard(zf_trainer_t* trainer, const float* x, const float* c, const float* w,
+                                   int64_t rows, int64_t global_rows, double* loss, float* gc, void* stream);
+
 /* Eval mode: the vector-Jacobian product of log_prob (flow.py:22-48 with
  * train=False) at the trainer's current blob — BatchNorm on the stored
  * mean / var, ShiftBounds on the stored xmin / xmax (no batch reductions, no

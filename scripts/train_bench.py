@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--optimizer", choices=("legacy", "chain", "clip"), default="legacy")
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--weighted", action="store_true", help="the weighted loss: Trainer.step(w=...)")
     args = ap.parse_args()
 
     from tests.flowcases import build_flow, make_case
@@ -56,17 +57,24 @@ def main():
             tr = Trainer(flow, case["variables"], cfg["D"], cfg["C"], B, optimizer=optimizer())
             xd = DeviceArray.from_numpy(np.ascontiguousarray(case["x"]))
             cd = None if case["c"] is None else DeviceArray.from_numpy(np.ascontiguousarray(case["c"]))
+            wd = None
+            if args.weighted:  # exponential weights, an eighth of them zero, a sixteenth negative
+                rng = np.random.default_rng(1005)
+                w = rng.exponential(1.0, B).astype(np.float32)
+                w[rng.choice(B, B // 8, replace=False)] = 0.0
+                w[rng.choice(B, B // 16, replace=False)] = -0.25
+                wd = DeviceArray.from_numpy(w)
             for _ in range(3):
-                tr.step(xd, cd)
+                tr.step(xd, cd, w=wd)
             for rep in range(args.reps):
                 L.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.steps):
-                    tr.step(xd, cd)
+                    tr.step(xd, cd, w=wd)
                 L.synchronize()
                 dt = (time.perf_counter() - t0) / args.steps
-                rec = {"config": name, "batch": B, "optimizer": args.optimizer, "ms_per_step": round(dt * 1e3, 4),
-                       "samples_per_s": round(B / dt), "loss": tr.last_loss()}
+                rec = {"config": name, "batch": B, "optimizer": args.optimizer, "weighted": bool(args.weighted),
+                       "ms_per_step": round(dt * 1e3, 4), "samples_per_s": round(B / dt), "loss": tr.last_loss()}
                 if args.tag:
                     rec["tag"] = args.tag
                 if args.reps > 1:

@@ -179,6 +179,8 @@ SIGNATURES = {
     "zf_trainer_step_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "zf_trainer_loss_grad_cond_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "zf_trainer_step_cond_shard": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "zf_trainer_loss_grad_weighted_shard": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "zf_trainer_step_weighted_shard": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "zf_trainer_log_prob_vjp": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "zf_trainer_get_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_blob": (_int, [_vp, _vp]),

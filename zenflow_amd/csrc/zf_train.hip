@@ -73,6 +73,7 @@ struct zf_trainer {
   // trainer's own buffers: x and c are copied in before the launch)
   hipStream_t cap = nullptr;
   std::map<int64_t, hipGraphExec_t> graphs;
+  std::map<int64_t, hipGraphExec_t> graphs_w;  // the weighted step's (it reads d_w as well)
   bool use_graph = true;
   bool bn_small = true;  // ZF_TRAIN_BN_SMALL=0: always the multi-launch BatchNorm path
   bool splitq = true;    // ZF_TRAIN_SPLITQ=0: never the split-set GEMM (same bits either way)
@@ -80,11 +81,12 @@ struct zf_trainer {
   float* d_g0 = nullptr;      // [bmax][D]
   float* d_g1 = nullptr;
   float* d_small = nullptr;   // per-column scratch (ShiftBounds min / max)
-  float* d_ce = nullptr;      // [bmax] per-row cotangent of the eval-mode VJP
+  float* d_ce = nullptr;      // [bmax] per-row cotangent of the eval-mode VJP / the weighted loss
+  float* d_w = nullptr;       // [bmax] per-row weights of the weighted loss
   double* d_leaf = nullptr;   // leaf partials of the BatchNorm sums / loss [kLeafCap][128]
   double* d_leaf2 = nullptr;  // first-level tree roots [kLeafCap / 64][128]
   double* d_ws2 = nullptr;    // first-level roots of the split-K partials
-  double* d_roots = nullptr;  // [0,128): tree roots of one reduction; [128]: the loss
+  double* d_roots = nullptr;  // [0,128): tree roots of one reduction; [128]: the loss; [129]: the weight sum
   double* d_rowloss = nullptr;  // [bmax] per-row loss terms
   double* d_g64 = nullptr;    // fp64 gradient accumulator (blob layout)
   // data parallelism: the communicator and its all-gather landing buffer
@@ -231,6 +233,7 @@ int zf_trainer_create(const zf_flow_desc* desc_in, const float* blob_host, int64
     nb.mean = zf::dmalloc(t, DC, rc);
     nb.rstd = zf::dmalloc(t, DC, rc);
   }
+  t->d_w = zf::dmalloc(t, B, rc);  // last: the buffers above keep the places they had without it
   hipError_t e = hipSuccess;
   if (!rc) e = hipMemcpy(t->d_nat, blob_host, need * sizeof(float), hipMemcpyHostToDevice);
   if (!rc && e == hipSuccess) e = hipMemcpy(t->d_mask, param_mask, need, hipMemcpyHostToDevice);
@@ -250,6 +253,7 @@ int zf_trainer_destroy(zf_trainer_t* t) {
   if (!t) return ZF_OK;
   (void)hipDeviceSynchronize();
   for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
+  for (auto& kv : t->graphs_w) (void)hipGraphExecDestroy(kv.second);
   if (t->cap) (void)hipStreamDestroy(t->cap);
   for (float* p : t->bufs) (void)hipFree(p);
   for (void* p : t->opt_bufs) (void)hipFree(p);
@@ -288,8 +292,10 @@ int zf_trainer_set_comm(zf_trainer_t* t, const zf_comm_desc* comm) {
 namespace zf {
 namespace {
 
-// Copy the batch into the trainer's buffers (state 0, d_c).
-int trainer_stage(zf_trainer_t* t, const float* x, const float* c, int64_t B64, hipStream_t st) {
+// Copy the batch into the trainer's buffers (state 0, d_c, and the rows'
+// weights into d_w when the loss is weighted).
+int trainer_stage(zf_trainer_t* t, const float* x, const float* c, int64_t B64, hipStream_t st,
+                  const float* w = nullptr) {
   if (!t) return einval("trainer is NULL");
   if (B64 < 1 || B64 > t->bmax) return einval("batch %lld outside [1, %lld]", (long long)B64, (long long)t->bmax);
   if (!x) return einval("x is NULL");
@@ -297,10 +303,12 @@ int trainer_stage(zf_trainer_t* t, const float* x, const float* c, int64_t B64, 
   ZF_TRY_HIP(hipMemcpyAsync(t->d_state, x, (size_t)B64 * t->D * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (t->C > 0)
     ZF_TRY_HIP(hipMemcpyAsync(t->d_c, c, (size_t)B64 * t->C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (w) ZF_TRY_HIP(hipMemcpyAsync(t->d_w, w, (size_t)B64 * sizeof(float), hipMemcpyDeviceToDevice, st));
   return ZF_OK;
 }
 
 inline double* loss_slot(zf_trainer_t* t) { return t->d_roots + 128; }
+inline double* wsum_slot(zf_trainer_t* t) { return t->d_roots + 129; }  // the weighted loss's sum of weights
 
 // Data parallelism: this rank's tree roots (n doubles, in place) -> the
 // global ones: all-gather every rank's roots, combine them by the top of the
@@ -390,8 +398,13 @@ struct DgradChain {
 // with respect to the conditions, as jax.grad(loss_fn_2) of
 // examples/deep_set.ipynb does through DeepSetFlow's c = phi(x)).  It only
 // adds stores: loss, G and the stepped blob keep their bits.
+// weighted: the loss is -sum_b w_b lp_b / sum_b w_b with the staged weights
+// d_w (the user's loss around flow.apply(..., train=True) for weighted
+// samples).  The weights enter at the loss only: the forward pass and its
+// batch statistics are the unweighted ones, and the reverse pass is seeded
+// with the per-row cotangent d_ce in place of the constant gl.
 int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* G, hipStream_t st,
-                 bool* step_in_cast = nullptr, float* gc = nullptr) {
+                 bool* step_in_cast = nullptr, float* gc = nullptr, bool weighted = false) {
   const int D = t->D, C = t->C, W = t->comm.world;
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
@@ -474,10 +487,24 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
     const Leaves ll = leaves_for(B, Bg, W, kLeafCap);
     // leaves that tile the 256-row blocks are summed inside the loss kernel
     const bool fused = ll.rows > 0 && ll.rows <= 256 && 256 % ll.rows == 0;
-    hipLaunchKernelGGL(zf::latent_loss_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, state(desc.n_ops),
-                       t->d_ld, B, Bg, D, rot, lc.lt, lc.a, lc.betac, lc.tnm, g, t->d_rowloss, fused ? ll.rows : 0, ll.n,
-                       t->d_leaf);
-    ZF_CHECK_LAUNCH("latent_loss_kernel");
+    if (weighted) {
+      // the sum of the weights over the loss's own leaf tree, then the rows' terms and cotangents
+      hipLaunchKernelGGL(leaf_sum_f32_kernel, dim3(blocks_for(ll.n, 64)), dim3(64), 0, st, (const float*)t->d_w, B,
+                         ll.rows, ll.n, t->d_leaf);
+      ZF_CHECK_LAUNCH("leaf_sum_f32_kernel");
+      if ((rc = launch_tree_cols(t->d_leaf, ll.n, 1, wsum_slot(t), st, t->d_leaf2))) return rc;
+      if ((rc = dp_combine(t, wsum_slot(t), 1, st))) return rc;
+      hipLaunchKernelGGL(zf::latent_loss_weighted_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st,
+                         state(desc.n_ops), t->d_ld, (const float*)t->d_w, (const double*)wsum_slot(t), B, D, rot,
+                         lc.lt, lc.a, lc.betac, lc.tnm, g, t->d_ce, t->d_rowloss, fused ? ll.rows : 0, ll.n,
+                         t->d_leaf);
+      ZF_CHECK_LAUNCH("latent_loss_weighted_kernel");
+    } else {
+      hipLaunchKernelGGL(zf::latent_loss_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, state(desc.n_ops),
+                         t->d_ld, B, Bg, D, rot, lc.lt, lc.a, lc.betac, lc.tnm, g, t->d_rowloss, fused ? ll.rows : 0,
+                         ll.n, t->d_leaf);
+      ZF_CHECK_LAUNCH("latent_loss_kernel");
+    }
     if (!fused) {
       hipLaunchKernelGGL(leaf_sum_kernel, dim3(blocks_for(ll.n, 64)), dim3(64), 0, st, t->d_rowloss, B, ll.rows,
                          ll.n, t->d_leaf);
@@ -505,7 +532,9 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
     zf_trainer::NscBufs& nb = t->nsc[i];
     const int r = rots[i];
     // spline: g -> g_prev (transformed columns), gP
-    rc = spline_bwd_launch<false>(state(i), nb.P, g, gl, g_prev, nb.gP, B, D, dt, op.knots, r, nullptr, st);
+    rc = weighted
+             ? spline_bwd_launch<true>(state(i), nb.P, g, 0.f, g_prev, nb.gP, B, D, dt, op.knots, r, t->d_ce, st)
+             : spline_bwd_launch<false>(state(i), nb.P, g, gl, g_prev, nb.gP, B, D, dt, op.knots, r, nullptr, st);
     if (rc) return rc;
     // MLP reverse
     DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
@@ -684,22 +713,25 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
   return ZF_OK;
 }
 
-// The whole step (body + optimiser) captured once per batch size.
-int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out) {
-  auto it = t->graphs.find(B);
-  if (it != t->graphs.end()) {
+// The whole step (body + optimiser) captured once per batch size; the
+// weighted step has a cache of its own, bounded the same way (weighted and
+// unweighted steps may alternate on one trainer).
+int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out, bool weighted = false) {
+  std::map<int64_t, hipGraphExec_t>& graphs = weighted ? t->graphs_w : t->graphs;
+  auto it = graphs.find(B);
+  if (it != graphs.end()) {
     *out = it->second;
     return ZF_OK;
   }
-  if (t->graphs.size() >= 8) {  // bound the cache (batch sizes rarely vary)
+  if (graphs.size() >= 8) {  // bound the cache (batch sizes rarely vary)
     ZF_TRY_HIP(hipStreamSynchronize(t->cap));
     ZF_TRY_HIP(hipDeviceSynchronize());
-    for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
-    t->graphs.clear();
+    for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
+    graphs.clear();
   }
   ZF_TRY_HIP(hipStreamBeginCapture(t->cap, hipStreamCaptureModeThreadLocal));
   bool stepped = false;
-  int rc = trainer_body(t, B, B, 1, t->d_grad, t->cap, t->chain_on ? nullptr : &stepped);
+  int rc = trainer_body(t, B, B, 1, t->d_grad, t->cap, t->chain_on ? nullptr : &stepped, nullptr, weighted);
   if (!rc) rc = trainer_update(t, t->cap, stepped);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(t->cap, &g);
@@ -711,7 +743,7 @@ int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out) {
   }
   if (g) (void)hipGraphDestroy(g);
   if (rc) return rc;
-  t->graphs[B] = exec;
+  graphs[B] = exec;
   *out = exec;
   return ZF_OK;
 }
@@ -796,6 +828,53 @@ int zf_trainer_step_cond_shard(zf_trainer_t* t, const float* x, const float* c, 
   rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped, gc);
   if (!rc) rc = zf::trainer_update(t, st, stepped);
   if (rc) return rc;
+  t->t += 1;
+  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
+  return ZF_OK;
+}
+
+// Weighted maximum likelihood: loss = -sum_b w_b lp_b / sum_b w_b over the
+// global batch, w this rank's `rows` weights (trainer_body, weighted).
+int zf_trainer_loss_grad_weighted_shard(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t rows,
+                                        int64_t global_rows, int update_stats, double* loss, float* grad, float* gc,
+                                        void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (!w) return zf_trainer_loss_grad_cond_shard(t, x, c, rows, global_rows, update_stats, loss, grad, gc, stream);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = zf::trainer_stage(t, x, c, rows, st, w);
+  if (rc) return rc;
+  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
+    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
+  rc = zf::trainer_body(t, (int)rows, global_rows, update_stats, grad ? grad : t->d_grad, st, nullptr, gc, true);
+  if (rc) return rc;
+  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
+  return ZF_OK;
+}
+
+// The weighted step replays its own captured graph per batch size (it reads
+// the staged weights at a fixed address); with gc, or a communicator, it is
+// launched eagerly, as zf_trainer_step_cond_shard is.
+int zf_trainer_step_weighted_shard(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t rows,
+                                   int64_t global_rows, double* loss, float* gc, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (!w) return zf_trainer_step_cond_shard(t, x, c, rows, global_rows, loss, gc, stream);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = zf::trainer_stage(t, x, c, rows, st, w);
+  if (rc) return rc;
+  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
+    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
+  if (t->C == 0) gc = nullptr;
+  if (!gc && t->use_graph && t->comm.world == 1) {
+    hipGraphExec_t exec = nullptr;
+    rc = zf::step_graph(t, (int)rows, &exec, true);
+    if (rc) return rc;
+    ZF_TRY_HIP(hipGraphLaunch(exec, st));
+  } else {
+    bool stepped = false;
+    rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped, gc, true);
+    if (!rc) rc = zf::trainer_update(t, st, stepped);
+    if (rc) return rc;
+  }
   t->t += 1;
   if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
   return ZF_OK;
@@ -969,6 +1048,8 @@ int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, con
   ZF_TRY_HIP(hipDeviceSynchronize());
   for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
   t->graphs.clear();
+  for (auto& kv : t->graphs_w) (void)hipGraphExecDestroy(kv.second);
+  t->graphs_w.clear();
   zf::free_chain(t);
   const size_t need = (size_t)t->nat_floats;
   int rc = ZF_OK;

@@ -554,6 +554,96 @@ __global__ __launch_bounds__(256) void latent_loss_kernel(const float* __restric
     for (int zl = (B + leaf_rows - 1) / leaf_rows + (int)threadIdx.x; zl < leaf_n; zl += 256) leaf[zl] = 0.0;
 }
 
+// ---- weighted latent + loss --------------------------------------------------
+// loss = -sum_b w_b lp_b / Wsum, Wsum = sum_b w_b over the global batch: the
+// loss a user of the reference writes around flow.apply(..., train=True) for
+// weighted samples (event weights, sWeights, importance weights; they may be
+// zero or negative, their sum must be positive).
+
+// Leaf sums of the fp32 weights, fp64 in row order (leaf_sum_kernel's leaves).
+__global__ void leaf_sum_f32_kernel(const float* __restrict__ x, int B, int rows, int n, double* __restrict__ p) {
+  const int z = blockIdx.x * blockDim.x + threadIdx.x;
+  if (z >= n) return;
+  const int b0 = min(B, z * rows), b1 = min(B, b0 + rows);
+  double a = 0.0;
+  for (int b = b0; b < b1; ++b) a += (double)x[b];
+  p[z] = a;
+}
+
+// latent_loss_kernel with a weight per row: lp as there (restated, as in
+// latent_vjp_kernel: the unweighted kernel keeps its code); the row's loss term
+// -w lp / Wsum (fp64: the product is exact, the quotient rounded once); its
+// cotangent ce = -w / Wsum (the fp64 quotient, rounded once) where lp is
+// finite before nan_to_num and 0 elsewhere (latent_vjp_kernel's `fin` rule),
+// which seeds gz = ce . d latent_lp / dz here and the log-det cotangent of
+// every coupling's spline reverse.  wsum: the global sum of the weights (one
+// double on the device).  The leaf sums as in latent_loss_kernel.
+__global__ __launch_bounds__(256) void latent_loss_weighted_kernel(
+    const float* __restrict__ z, const float* __restrict__ ld, const float* __restrict__ w,
+    const double* __restrict__ wsum, int B, int D, int rot, int latent, float a, float betac, float tnmass,
+    float* __restrict__ gz, float* __restrict__ ce, double* __restrict__ row_loss, int leaf_rows, int leaf_n,
+    double* __restrict__ leaf) {
+  __shared__ double rl[256];
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) {
+    float lat = 0.f;
+    for (int j = 0; j < D; ++j) {
+      const float v = z[(long long)b * D + pmodi(j + rot, D)];
+      float t;
+      if (latent == ZF_LATENT_NORMAL || latent == ZF_LATENT_TRUNCNORM) {
+        const float dv = v - 0.5f;
+        t = (logf(6.28318530717958647692f * 0.01f) + (dv * dv) / 0.01f) / -2.0f;
+        if (latent == ZF_LATENT_TRUNCNORM) {
+          t = t - tnmass;
+          if (dv / 0.1f < -5.f || dv / 0.1f > 5.f) t = -INFINITY;
+        }
+      } else if (latent == ZF_LATENT_BETA) {
+        const float am1 = a - 1.0f;
+        t = betac + (am1 == 0.f ? 0.f : am1 * logf(v)) + (am1 == 0.f ? 0.f : am1 * log1pf(-v));
+        if (v > 1.f || v < 0.f) t = -INFINITY;
+      } else {
+        t = (v > 1.f || v < 0.f) ? -INFINITY : 0.f;
+      }
+      lat = lat + t;
+    }
+    float lp = lat + ld[b];
+    const bool fin = (lp == lp) && lp != INFINITY && lp != -INFINITY;
+    if (lp != lp) lp = -INFINITY;
+    if (lp == INFINITY) lp = 3.40282347e38f;
+    if (lp == -INFINITY) lp = -3.40282347e38f;
+    const double W = *wsum, wb = (double)w[b];
+    const double term = -(wb * (double)lp) / W;
+    row_loss[b] = term;
+    const float s = fin ? (float)(-wb / W) : 0.f;
+    ce[b] = s;
+    for (int j = 0; j < D; ++j) {
+      const int col = pmodi(j + rot, D);
+      const float v = z[(long long)b * D + col];
+      float g = 0.f;
+      if (fin) {
+        if (latent == ZF_LATENT_NORMAL || latent == ZF_LATENT_TRUNCNORM) g = -(v - 0.5f) / 0.01f;
+        else if (latent == ZF_LATENT_BETA) g = (a - 1.0f) / v - (a - 1.0f) / (1.0f - v);
+      }
+      gz[(long long)b * D + col] = s * g;
+    }
+    rl[threadIdx.x] = term;
+  }
+  if (leaf_rows <= 0) return;
+  __syncthreads();
+  const int per = 256 / leaf_rows, z0 = blockIdx.x * 256;
+  if ((int)threadIdx.x < per) {
+    const int r0 = z0 + threadIdx.x * leaf_rows;
+    if (r0 < B) {
+      const int r1 = min(B, r0 + leaf_rows);
+      double acc = 0.0;
+      for (int r = r0; r < r1; ++r) acc += rl[r - z0];
+      leaf[r0 / leaf_rows] = acc;
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1)  // the leaves past the last row are empty (0, as leaf_sum_kernel)
+    for (int zl = (B + leaf_rows - 1) / leaf_rows + (int)threadIdx.x; zl < leaf_n; zl += 256) leaf[zl] = 0.0;
+}
+
 // ShiftBounds batch min / max of every rank (all-gathered [world][2][64]:
 // min row, max row) -> the global min / max (a NaN anywhere stays NaN).
 __global__ void minmax_ranks_kernel(const float* __restrict__ gath, int world, int D, float* __restrict__ cmin,

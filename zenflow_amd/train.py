@@ -149,8 +149,17 @@ class Trainer:
     def _global(self, rows: int, global_rows: Optional[int]) -> int:
         return int(global_rows) if global_rows is not None else int(rows) * self.world
 
+    def _weights(self, w, rows: int) -> DeviceArray:
+        """This rank's ``rows`` weights on the device.  A host array is checked
+        (shape, finiteness); a DeviceArray is taken as it is, size apart."""
+        if isinstance(w, DeviceArray):
+            if int(np.prod(w.shape)) != rows or w.dtype != np.float32:
+                raise ValueError(f"w must hold {rows} float32 weights, got {w.dtype} {w.shape}")
+            return w
+        return DeviceArray.from_numpy(check_weights(w, rows, "w"))
+
     def loss_grad(self, x, c=None, update_stats: bool = False,
-                  global_rows: Optional[int] = None, cond_grad: bool = False):
+                  global_rows: Optional[int] = None, cond_grad: bool = False, w=None):
         """(loss, gradient in the natural blob layout) — loss_fn + jax.grad.
         Data parallel: ``x`` is this rank's shard of a global batch of
         ``global_rows`` rows (default: equal shards); both results are global.
@@ -159,10 +168,28 @@ class Trainer:
         d loss / d c of this rank's rows — what ``jax.grad(loss_fn_2)`` of
         examples/deep_set.ipynb sends back into ``phi`` through
         ``c = phi(x)``; a DeviceArray when ``c`` was one.  loss and grad have
-        the same bits either way."""
+        the same bits either way.
+
+        ``w`` (rows,), a host array or a DeviceArray: per-sample weights of
+        this rank's rows; the loss is ``-sum(w * lp) / sum(w)`` over the global
+        batch (weights may be zero or negative, their sum must be positive).
+        The batch statistics stay unweighted: the weights enter at the loss
+        only."""
         xd, cd = self._dev(x, self.D), self._dev(c, self.C)
         g = DeviceArray((self.program.blob.size,))
         rows = xd.shape[0]
+        if w is not None:
+            wd = self._weights(w, rows)
+            gc = self._gc_out(rows) if cond_grad else None
+            check(L.load_library().zf_trainer_loss_grad_weighted_shard(
+                self.handle, xd.ptr, None if cd is None else cd.ptr, wd.ptr, rows, self._global(rows, global_rows),
+                1 if update_stats else 0, self._loss.ptr, g.ptr, None if gc is None else gc.ptr, L.stream()),
+                "zf_trainer_loss_grad_weighted")
+            self._last_rows = None  # the weighted loss is the device's fp64 value as is
+            loss = float(self._loss.numpy()[0])
+            if cond_grad:
+                return loss, g.numpy(), (gc if isinstance(c, DeviceArray) else gc.numpy())
+            return loss, g.numpy()
         if cond_grad:
             gc = self._gc_out(rows)
             check(L.load_library().zf_trainer_loss_grad_cond_shard(
@@ -187,17 +214,25 @@ class Trainer:
         """Gradient blob -> FLAX ``params`` tree (like jax.grad's output)."""
         return {"bijector": self.program.blob_to_variables(grad_blob)["params"]}
 
-    def step(self, x, c=None, global_rows: Optional[int] = None, cond_grad: bool = False):
+    def step(self, x, c=None, global_rows: Optional[int] = None, cond_grad: bool = False, w=None):
         """One optimiser step (train.py:80-86).  ``cond_grad=True`` returns
         ``gc`` (rows, C) = d loss / d c of the loss this step descended (a
         DeviceArray when ``c`` was one); the stepped parameters have the same
-        bits either way."""
+        bits either way.  ``w``: per-sample weights, as in :meth:`loss_grad`."""
         xd, cd = self._dev(x, self.D), self._dev(c, self.C)
-        if not cond_grad:
-            self._step_rows(xd.ptr, None if cd is None else cd.ptr, xd.shape[0], global_rows)
-            return None
         rows = xd.shape[0]
+        wd = None if w is None else self._weights(w, rows)
+        if not cond_grad:
+            self._step_rows(xd.ptr, None if cd is None else cd.ptr, rows, global_rows,
+                            None if wd is None else wd.ptr)
+            return None
         gc = self._gc_out(rows)
+        if wd is not None:
+            self._last_rows = None
+            check(L.load_library().zf_trainer_step_weighted_shard(
+                self.handle, xd.ptr, cd.ptr, wd.ptr, rows, self._global(rows, global_rows), self._loss.ptr, gc.ptr,
+                L.stream()), "zf_trainer_step_weighted")
+            return gc if isinstance(c, DeviceArray) else gc.numpy()
         self._last_rows = self._global(rows, global_rows)
         check(L.load_library().zf_trainer_step_cond_shard(self.handle, xd.ptr, cd.ptr, rows,
                                                           self._global(rows, global_rows), self._loss.ptr, gc.ptr,
@@ -222,13 +257,21 @@ class Trainer:
             dx.ptr, None if dc is None else dc.ptr, N, L.stream()), "zf_trainer_log_prob_vjp")
         return lp, dx, dc
 
-    def _step_rows(self, xptr: int, cptr: Optional[int], rows: int, global_rows: Optional[int] = None) -> None:
-        """One step on ``rows`` device-resident rows (raw pointers; async)."""
+    def _step_rows(self, xptr: int, cptr: Optional[int], rows: int, global_rows: Optional[int] = None,
+                   wptr: Optional[int] = None) -> None:
+        """One step on ``rows`` device-resident rows (raw pointers; async);
+        ``wptr``: their weights (the weighted loss)."""
+        if wptr is not None:
+            self._last_rows = None
+            check(L.load_library().zf_trainer_step_weighted_shard(
+                self.handle, xptr, cptr, wptr, rows, self._global(rows, global_rows), self._loss.ptr, None,
+                L.stream()), "zf_trainer_step_weighted")
+            return
         self._last_rows = self._global(rows, global_rows)
         check(L.load_library().zf_trainer_step_shard(self.handle, xptr, cptr, rows, self._global(rows, global_rows),
                                                      self._loss.ptr, L.stream()), "zf_trainer_step")
 
-    def _step_local(self, xptr: int, cptr: Optional[int], rows: int) -> None:
+    def _step_local(self, xptr: int, cptr: Optional[int], rows: int, wptr: Optional[int] = None) -> None:
         """One step on the whole batch without the cross-rank reductions:
         every rank holds the same batch, so each computes the one-device
         step itself (a batch with fewer rows than ranks)."""
@@ -236,9 +279,14 @@ class Trainer:
         if self.world > 1:
             check(lib.zf_trainer_set_comm(self.handle, None), "zf_trainer_set_comm")
         try:
-            self._last_rows = rows
-            check(lib.zf_trainer_step_shard(self.handle, xptr, cptr, rows, rows, self._loss.ptr, L.stream()),
-                  "zf_trainer_step")
+            if wptr is not None:
+                self._last_rows = None
+                check(lib.zf_trainer_step_weighted_shard(self.handle, xptr, cptr, wptr, rows, rows, self._loss.ptr,
+                                                         None, L.stream()), "zf_trainer_step_weighted")
+            else:
+                self._last_rows = rows
+                check(lib.zf_trainer_step_shard(self.handle, xptr, cptr, rows, rows, self._loss.ptr, L.stream()),
+                      "zf_trainer_step")
         finally:
             if self.world > 1:
                 check(lib.zf_trainer_set_comm(self.handle, ct.byref(self._comm_desc)), "zf_trainer_set_comm")
@@ -250,7 +298,8 @@ class Trainer:
         """The device loss is -sum(lp / B) in fp64; the reference's loss_fn
         (train.py:70-72) is jnp.mean in fp32, whose sum overflows to +-inf once
         |sum(lp)| leaves the fp32 range (two rows at finfo.min) — the same rule
-        as dist.nll_from_sum, applied to the global batch of the last call."""
+        as dist.nll_from_sum, applied to the global batch of the last call.
+        A weighted loss (``_last_rows`` None) is returned as it is."""
         from .dist import nll_from_sum
 
         B = getattr(self, "_last_rows", None)
@@ -300,11 +349,33 @@ class Trainer:
         check(lib.zf_trainer_set_opt_count(self.handle, int(state["count"])), "zf_trainer_set_opt_count")
 
 
-def _metric(flow, variables, x, c) -> float:
-    """metric_fn (train.py:74-78): -mean(log_prob), eval mode."""
+def check_weights(w, rows: int, name: str) -> np.ndarray:
+    """``w`` as a contiguous float32 array of shape (rows,), all finite
+    (ValueError otherwise); zero and negative weights are allowed."""
+    a = np.asarray(w)
+    if a.shape != (rows,):
+        raise ValueError(f"{name} must have shape ({rows},), got {a.shape}")
+    a = np.ascontiguousarray(a, np.float32)
+    if not np.isfinite(a).all():
+        raise ValueError(f"{name} holds {int((~np.isfinite(a)).sum())} non-finite weights")
+    return a
+
+
+def weighted_nll(lp, w) -> float:
+    """-sum(w * lp) / sum(w) in fp64: the weighted metric."""
+    lp = np.asarray(lp, np.float64)
+    w = np.asarray(w, np.float64)
+    return float(-(w * lp).sum() / w.sum())
+
+
+def _metric(flow, variables, x, c, w=None) -> float:
+    """metric_fn (train.py:74-78): -mean(log_prob), eval mode; with weights
+    ``w`` the weighted mean :func:`weighted_nll`."""
     from .dist import nll_from_sum
 
     lp = np.asarray(flow.apply(variables, x, c), np.float64)
+    if w is not None:
+        return weighted_nll(lp, w)
     return nll_from_sum(lp.sum(), lp.shape[0])
 
 
@@ -324,6 +395,8 @@ def train(
     progress: bool = True,
     initial_variables=None,
     comm=None,
+    W_train=None,
+    W_test=None,
 ) -> Tuple[Dict[str, Any], int, List[float], List[float]]:
     """Trains the normalizing flow on the provided inputs (train.py:18-138).
 
@@ -340,7 +413,16 @@ def train(
     reductions make every rank's parameters identical after every step, and
     equal to one device's when every batch splits evenly.  A batch with fewer
     rows than ranks is stepped by every rank on the whole batch, without
-    reductions (the one-device step)."""
+    reductions (the one-device step).
+
+    ``W_train`` (n_train,), ``W_test`` (n_test,): per-sample weights — event
+    weights, sWeights, importance or class-balance weights.  With the
+    reference this is the user's own ``loss_fn``, ``-(w * lp).sum() / w.sum()``;
+    here every step descends that loss of its batch (``Trainer.step(w=...)``:
+    the batch statistics stay unweighted), ``loss_train`` is the weighted
+    metric of the last batch, and ``loss_test`` is weighted by ``W_test``
+    when given.  Weights may be zero or negative; every batch's weights must
+    sum to a positive number (checked per epoch, ``ValueError``)."""
     if warmup < 1:
         warmup = warmup * epochs
     warmup = int(warmup)
@@ -356,6 +438,13 @@ def train(
         C_train = C_train.reshape(-1, 1)
     if C_test is not None and C_test.ndim == 1:
         C_test = C_test.reshape(-1, 1)
+    # the weights are checked before any device call
+    if W_train is not None:
+        W_train = check_weights(W_train, X_train.shape[0], "W_train")
+    if W_test is not None:
+        W_test = check_weights(W_test, X_test.shape[0], "W_test")
+        if not W_test.astype(np.float64).sum() > 0:
+            raise ValueError("W_test must sum to a positive number")
 
     if initial_variables is None:
         variables = flow.init(PRNGKey(seed), X_train[:1], None if C_train is None else C_train[:1])
@@ -387,27 +476,37 @@ def train(
         perm = np.random.default_rng([seed, epoch]).permutation(n)
         X_perm = X_train[perm]
         C_perm = None if C_train is None else C_train[perm]
+        W_perm = None if W_train is None else W_train[perm]
+        if W_perm is not None:
+            sums = np.add.reduceat(W_perm.astype(np.float64), np.arange(0, n, batch_size))
+            if not (sums > 0).all():
+                k = int(np.argmin(sums > 0))
+                raise ValueError(f"epoch {epoch}: the weights of batch {k} sum to {sums[k]:.6g}, not a positive number")
         # one upload per epoch; batches are row ranges of the resident copy
         X_dev = DeviceArray.from_numpy(X_perm)
         C_dev = None if C_perm is None else DeviceArray.from_numpy(C_perm)
+        W_dev = None if W_perm is None else DeviceArray.from_numpy(W_perm)
         for batch_idx in range(0, n, batch_size):
             rows = min(batch_size, n - batch_idx)
             if rows < world:
                 trainer._step_local(X_dev.ptr + batch_idx * D * 4,
-                                    None if C_dev is None else C_dev.ptr + batch_idx * Cd * 4, rows)
+                                    None if C_dev is None else C_dev.ptr + batch_idx * Cd * 4, rows,
+                                    None if W_dev is None else W_dev.ptr + batch_idx * 4)
                 continue
             if rows % world and epoch == 0:
                 warnings.warn(f"batch of {rows} rows does not split evenly over {world} ranks: ranks stay "
                               "identical but their fp64 reduction order differs from one device's", RuntimeWarning)
             lo, hi = shard_rows(rows, rank, world)
             trainer._step_rows(X_dev.ptr + (batch_idx + lo) * D * 4,
-                               None if C_dev is None else C_dev.ptr + (batch_idx + lo) * Cd * 4, hi - lo, rows)
+                               None if C_dev is None else C_dev.ptr + (batch_idx + lo) * Cd * 4, hi - lo, rows,
+                               None if W_dev is None else W_dev.ptr + (batch_idx + lo) * 4)
         X = X_perm[batch_idx : batch_idx + batch_size]
         C = None if C_perm is None else C_perm[batch_idx : batch_idx + batch_size]
+        W = None if W_perm is None else W_perm[batch_idx : batch_idx + batch_size]
 
         variables = trainer.variables()
-        loss_train.append(_metric(flow, variables, X, C))  # last batch, as train.py:122
-        loss_test.append(_metric(flow, variables, X_test, C_test))
+        loss_train.append(_metric(flow, variables, X, C, W))  # last batch, as train.py:122
+        loss_test.append(_metric(flow, variables, X_test, C_test, W_test))
 
         if not np.isfinite(loss_train[-1]):
             warnings.warn(f"epoch {epoch}: loss[train] not finite, abort training", RuntimeWarning)
