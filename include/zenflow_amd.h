@@ -340,7 +340,9 @@ int zf_trainer_set_comm(zf_trainer_t* trainer, const zf_comm_desc* comm);
 /* loss_grad / step on this rank's `rows` rows of a global batch of
  * `global_rows` rows (the loss is -mean over the global batch; the gradient
  * and loss returned are the global ones, identical on every rank).  The
- * plain entries above use global_rows = rows * world. */
+ * plain entries above use global_rows = rows * world.  Every loss_grad /
+ * step entry checks its arguments first: a call that returns ZF_EINVAL for
+ * them has enqueued nothing on the stream. */
 int zf_trainer_loss_grad_shard(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows,
                                int64_t global_rows, int update_stats, double* loss, float* grad, void* stream);
 int zf_trainer_step_shard(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows, int64_t global_rows,

@@ -212,6 +212,25 @@ def build_flow(cfg):
     return zf.Flow(bi.Chain(mods), latent=latent)
 
 
+def _trainer(case, N, **kw):
+    """A Trainer on a case's flow and variables, for batches of up to N rows."""
+    from zenflow_amd.train import Trainer
+
+    cfg = case["cfg"]
+    flow = build_flow(cfg)
+    flow.latent._dim = cfg["D"]
+    return Trainer(flow, case["variables"], cfg["D"], cfg["C"], N, **kw)
+
+
+def _blob(tr):
+    """The trainer's current blob (parameters and statistics), on the host."""
+    from zenflow_amd import _lib as L
+
+    blob = np.empty_like(tr.program.blob)
+    L.check(L.load_library().zf_trainer_get_blob(tr.handle, blob.ctypes.data), "get_blob")
+    return blob
+
+
 # --- nested Flow (examples/deep_set.ipynb:318-328): a user module holding a Flow
 def make_deep_set_module():
     """DeepSetFlow of the reference's deep-set example, restated on the

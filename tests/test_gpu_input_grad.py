@@ -31,7 +31,7 @@ import numpy as np
 import pytest
 
 from tests.flowcases import bounded_case as _bounded_case
-from tests.flowcases import build_flow, make_case
+from tests.flowcases import _blob, _trainer, build_flow, make_case
 from tests.input_grad_oracle import pack_job
 
 pytestmark = pytest.mark.gpu
@@ -220,23 +220,6 @@ def test_large_batch():
 
 
 # ---- train mode: d loss / d c ----------------------------------------------------
-def _trainer(case, N, **kw):
-    from zenflow_amd.train import Trainer
-
-    cfg = case["cfg"]
-    flow = build_flow(cfg)
-    flow.latent._dim = cfg["D"]
-    return Trainer(flow, case["variables"], cfg["D"], cfg["C"], N, **kw)
-
-
-def _blob(tr):
-    from zenflow_amd import _lib as L
-
-    blob = np.empty_like(tr.program.blob)
-    L.check(L.load_library().zf_trainer_get_blob(tr.handle, blob.ctypes.data), "get_blob")
-    return blob
-
-
 @pytest.mark.parametrize("bn_small", ["1", "0"])
 @pytest.mark.parametrize("name,N,seed", [("cfg4", 128, 12), ("odd", 300, 13), ("deep", 256, 14)])
 def test_train_gc(name, N, seed, bn_small, monkeypatch):

@@ -23,7 +23,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from tests.flowcases import build_flow, make_case
+from tests.flowcases import _blob, _trainer, make_case
 from tests.weighted_grad_oracle import make_weights
 
 pytestmark = pytest.mark.gpu
@@ -40,23 +40,6 @@ def oracle(name, N, seed):
         subprocess.run([sys.executable, "-m", "tests.weighted_grad_oracle", name, str(N), str(seed), str(out)],
                        cwd=ROOT, check=True, timeout=600)
         return dict(np.load(out))
-
-
-def _trainer(case, N, **kw):
-    from zenflow_amd.train import Trainer
-
-    cfg = case["cfg"]
-    flow = build_flow(cfg)
-    flow.latent._dim = cfg["D"]
-    return Trainer(flow, case["variables"], cfg["D"], cfg["C"], N, **kw)
-
-
-def _blob(tr):
-    from zenflow_amd import _lib as L
-
-    blob = np.empty_like(tr.program.blob)
-    L.check(L.load_library().zf_trainer_get_blob(tr.handle, blob.ctypes.data), "get_blob")
-    return blob
 
 
 def _get(tree, path):

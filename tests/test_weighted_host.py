@@ -85,6 +85,22 @@ def test_new_symbols_bound_and_exported():
         assert hasattr(lib, name), name
 
 
+def test_every_entry_rejects_a_null_trainer():
+    """Each of the eight loss_grad / step entries, called with a NULL trainer
+    (no device is touched): -1 and "trainer is NULL"."""
+    lib = L.load_library()
+    entries = [n for n in L.SIGNATURES if n.startswith(("zf_trainer_loss_grad", "zf_trainer_step"))]
+    assert len(entries) == 8
+    for name in entries:
+        _, args = L.SIGNATURES[name]
+        zeros = [0 if a in (L.C.c_int, L.C.c_int64) else None for a in args]
+        assert getattr(lib, name)(*zeros) == -1, name
+        assert "trainer is NULL" in lib.zf_last_error().decode(), name
+        # another message in between: the next entry must set its own
+        assert lib.zf_trainer_get_blob(None, None) == -1
+        assert "trainer is NULL" not in lib.zf_last_error().decode()
+
+
 def test_signatures():
     from zenflow_amd.train import Trainer, train
 

@@ -53,6 +53,8 @@ struct zf_trainer {
   std::vector<float*> bufs;
   std::vector<int64_t> sizes;
   float* d_state = nullptr;   // [n_ops + 1][bmax][D] states before each op
+  std::vector<float*> sp;     // sp[i]: the state before op i (Roll is an index rotation: it aliases its input)
+  std::vector<int> rots;      // rots[i]: the column rotation before op i; rots[n_ops]: the latent's
   float* d_c = nullptr;       // [bmax][C] conditioning inputs of the batch
   float* d_bc = nullptr;      // optimiser step count + bias corrections (step_kernel)
   // optimiser chain (zf_trainer_set_optim_chain); off: the (n)adamw of `opt`
@@ -120,12 +122,17 @@ float* dmalloc(zf_trainer* t, int64_t n, int& rc) {
   return (float*)p;
 }
 
-int nsc_dims(const zf_trainer* t, const zf_op_desc& op, int& dt, int& dc, int& DC, int& S) {
+void nsc_dims(const zf_trainer* t, const zf_op_desc& op, int& dt, int& dc, int& DC, int& S) {
   dt = t->D / 2;
   dc = t->D - dt;
   DC = dc + t->C;
   S = 3 * op.knots - 1;
-  return ZF_OK;
+}
+
+// Destroy every captured step of one cache (the caller has synchronised).
+void drop_graphs(std::map<int64_t, hipGraphExec_t>& graphs) {
+  for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
+  graphs.clear();
 }
 
 }  // namespace
@@ -245,6 +252,14 @@ int zf_trainer_create(const zf_flow_desc* desc_in, const float* blob_host, int64
     zf_trainer_destroy(t);
     return rc;
   }
+  // the coupling chain's state pointers and rotations depend on desc and bmax only
+  t->sp.assign(desc.n_ops + 1, t->d_state);
+  t->rots.assign(desc.n_ops + 1, 0);
+  for (int i = 0; i < desc.n_ops; ++i) {
+    const bool roll = desc.ops[i].kind == ZF_OP_ROLL;
+    t->sp[i + 1] = roll ? t->sp[i] : t->d_state + (int64_t)(i + 1) * B * D;
+    t->rots[i + 1] = roll ? zf::pmodi(t->rots[i] - desc.ops[i].shift, (int)D) : t->rots[i];
+  }
   *out = t;
   return ZF_OK;
 }
@@ -252,8 +267,8 @@ int zf_trainer_create(const zf_flow_desc* desc_in, const float* blob_host, int64
 int zf_trainer_destroy(zf_trainer_t* t) {
   if (!t) return ZF_OK;
   (void)hipDeviceSynchronize();
-  for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
-  for (auto& kv : t->graphs_w) (void)hipGraphExecDestroy(kv.second);
+  zf::drop_graphs(t->graphs);
+  zf::drop_graphs(t->graphs_w);
   if (t->cap) (void)hipStreamDestroy(t->cap);
   for (float* p : t->bufs) (void)hipFree(p);
   for (void* p : t->opt_bufs) (void)hipFree(p);
@@ -292,14 +307,34 @@ int zf_trainer_set_comm(zf_trainer_t* t, const zf_comm_desc* comm) {
 namespace zf {
 namespace {
 
-// Copy the batch into the trainer's buffers (state 0, d_c, and the rows'
-// weights into d_w when the loss is weighted).
-int trainer_stage(zf_trainer_t* t, const float* x, const float* c, int64_t B64, hipStream_t st,
-                  const float* w = nullptr) {
+// One loss_grad / step call, as the widest C entry states it: this rank's
+// rows of a global batch, their weights (NULL: the unweighted loss) and the
+// outputs (grad NULL: the trainer's own; gc NULL or C == 0: no d loss / d c).
+struct BatchArgs {
+  const float *x, *c, *w;
+  int64_t rows, global_rows;
+  int update_stats;
+  double* loss;
+  float *grad, *gc;
+  hipStream_t stream;
+};
+
+// Everything that can be wrong with a batch, before anything is enqueued.
+int check_batch(const zf_trainer_t* t, const BatchArgs& a) {
   if (!t) return einval("trainer is NULL");
-  if (B64 < 1 || B64 > t->bmax) return einval("batch %lld outside [1, %lld]", (long long)B64, (long long)t->bmax);
-  if (!x) return einval("x is NULL");
-  if (t->C > 0 && !c) return einval("flow is conditional but c is NULL");
+  if (a.rows < 1 || a.rows > t->bmax)
+    return einval("batch %lld outside [1, %lld]", (long long)a.rows, (long long)t->bmax);
+  if (!a.x) return einval("x is NULL");
+  if (t->C > 0 && !a.c) return einval("flow is conditional but c is NULL");
+  if (a.global_rows < a.rows || (t->comm.world == 1 && a.global_rows != a.rows))
+    return einval("global_rows %lld vs rows %lld (world %d)", (long long)a.global_rows, (long long)a.rows,
+                  t->comm.world);
+  return ZF_OK;
+}
+
+// Copy B64 checked rows into the trainer's buffers (state 0, d_c, and the
+// rows' weights into d_w when the loss is weighted).
+int trainer_stage(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t B64, hipStream_t st) {
   ZF_TRY_HIP(hipMemcpyAsync(t->d_state, x, (size_t)B64 * t->D * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (t->C > 0)
     ZF_TRY_HIP(hipMemcpyAsync(t->d_c, c, (size_t)B64 * t->C * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -324,16 +359,6 @@ int dp_combine(zf_trainer_t* t, double* roots, long long n, hipStream_t st) {
 
 // ---- The coupling chain shared by the train-mode step (trainer_body) and the
 // eval-mode input gradients (trainer_vjp_chunk) ----
-
-// sp[i]: the state before op i; Roll is an index rotation, so it aliases its input.
-std::vector<float*> state_table(const zf_trainer_t* t) {
-  const zf_flow_desc& desc = t->desc;
-  std::vector<float*> sp(desc.n_ops + 1);
-  sp[0] = t->d_state;
-  for (int i = 0; i < desc.n_ops; ++i)
-    sp[i + 1] = desc.ops[i].kind == ZF_OP_ROLL ? sp[i] : t->d_state + (int64_t)(i + 1) * t->bmax * t->D;
-  return sp;
-}
 
 // The Dense chain of one coupling's conditioner: nb.Ubn -> Z[l], H[l] = act(Z[l]) -> nb.P
 // (dt * S raw spline parameters per row).  Bg: the batch that picks the GEMM form.
@@ -391,27 +416,30 @@ struct DgradChain {
 // Train-mode forward + loss + reverse pass from the staged batch of B rows
 // (this rank's shard of a global batch of Bg rows); the loss lands in
 // loss_slot(t), the gradient in G (natural blob layout, fp32).
-// step_in_cast: an optimiser update follows; the one-device gradient cast
-// advances its step counter (trainer_update then skips step_kernel).
-// gc (this rank's (B, C) rows, or NULL): also d loss / d c, the condition
+// step_in_cast (one device, an (n)adamw update follows): the gradient cast also
+// advances the optimiser's step counter, and trainer_update skips step_kernel.
+// a.gc (this rank's (B, C) rows, or NULL): also d loss / d c, the condition
 // columns of every coupling's d loss / d U (train.py:64-86 differentiated
 // with respect to the conditions, as jax.grad(loss_fn_2) of
 // examples/deep_set.ipynb does through DeepSetFlow's c = phi(x)).  It only
 // adds stores: loss, G and the stepped blob keep their bits.
-// weighted: the loss is -sum_b w_b lp_b / sum_b w_b with the staged weights
+// a.w != NULL: the loss is -sum_b w_b lp_b / sum_b w_b with the staged weights
 // d_w (the user's loss around flow.apply(..., train=True) for weighted
 // samples).  The weights enter at the loss only: the forward pass and its
 // batch statistics are the unweighted ones, and the reverse pass is seeded
 // with the per-row cotangent d_ce in place of the constant gl.
-int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* G, hipStream_t st,
-                 bool* step_in_cast = nullptr, float* gc = nullptr, bool weighted = false) {
-  const int D = t->D, C = t->C, W = t->comm.world;
+int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cast) {
+  const int D = t->D, C = t->C, W = t->comm.world, B = (int)a.rows, update_stats = a.update_stats;
+  const long long Bg = a.global_rows;
+  hipStream_t st = a.stream;
+  float* const gc = C > 0 ? a.gc : nullptr;
+  const bool weighted = a.w != nullptr;
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
   float* nat = t->d_nat;
   double* G64 = t->d_g64;
-  const std::vector<float*> sp = state_table(t);
-  auto state = [&](int i) { return sp[i]; };
+  const std::vector<int>& rots = t->rots;
+  auto state = [&](int i) { return t->sp[i]; };
   // a leading ShiftBounds sets ld itself (sb_forward_kernel, first)
   if (desc.n_ops == 0 || desc.ops[0].kind != ZF_OP_SHIFT_BOUNDS)
     ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
@@ -420,16 +448,13 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
   const bool small_ok = W == 1 && t->bn_small;
   int rc;
   // ---- forward (train mode) ----
-  int rot = 0;
-  std::vector<int> rots(desc.n_ops + 1, 0);
   for (int i = 0; i < desc.n_ops; ++i) {
     const zf_op_desc& op = desc.ops[i];
-    rots[i] = rot;
+    if (op.kind == ZF_OP_ROLL) continue;  // an index rotation: rots[i + 1]
+    const int rot = rots[i];
     float* sin = state(i);
     float* sout = state(i + 1);
-    if (op.kind == ZF_OP_ROLL) {
-      rot = zf::pmodi(rot - op.shift, D);
-    } else if (op.kind == ZF_OP_SHIFT_BOUNDS) {
+    if (op.kind == ZF_OP_SHIFT_BOUNDS) {
       float* sb = nat + op.off_sb;
       // batch min / max of the (safe_log-transformed) columns (first op: rot == 0)
       rc = zf_colstats(sin, B, D, D, 0, t->sb_modes.data(), t->sb_prm.data(), t->d_small, t->d_small + 64,
@@ -478,7 +503,7 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
       return zf::einval("op %d: unknown kind", i);
     }
   }
-  rots[desc.n_ops] = rot;
+  const int rot = rots[desc.n_ops];
   // ---- latent + loss ----
   const LatentConsts lc(desc);
   float* g = t->d_g0;
@@ -522,7 +547,6 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
   zf::WgradQueue wq;
   wq.tb.count = 0;
   wq.gq.count = 0;
-  if (C == 0) gc = nullptr;
   int gc_assign = 1;  // the first coupling met (the last of the chain) assigns gc
   for (int i = desc.n_ops - 1; i >= 0; --i) {
     const zf_op_desc& op = desc.ops[i];
@@ -601,13 +625,12 @@ int trainer_body(zf_trainer_t* t, int B, long long Bg, int update_stats, float* 
     hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, G64,
                        (long long)t->nat_floats, G, step_in_cast ? t->d_bc : nullptr, t->opt.b1, t->opt.b2);
     ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
-    if (step_in_cast) *step_in_cast = true;
   }
   return ZF_OK;
 }
 
 // The chain's step (zf_optim.hip): the gradient is in t->d_grad, its cast did
-// not step (trainer_body with step_in_cast = nullptr).
+// not step (trainer_body without step_in_cast).
 int chain_update(zf_trainer_t* t, hipStream_t st) {
   return optim_chain_step(t->d_nat, t->d_grad, t->d_mask, t->d_dmask, (long long)t->nat_floats, t->cargs,
                           t->chain_form, t->chain_clip, t->max_norm, t->chain_lr, t->sched, t->chain_adam,
@@ -636,26 +659,24 @@ int trainer_update(zf_trainer_t* t, hipStream_t st, bool step_done = false) {
 // on how many rows share the chunk only.
 int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const float* cot, float* lp_out, float* gx,
                       float* gc, int B, hipStream_t st) {
-  int rc = trainer_stage(t, x, c_in, B, st);
+  int rc = trainer_stage(t, x, c_in, nullptr, B, st);  // checked by zf_trainer_log_prob_vjp
   if (rc) return rc;
   const int D = t->D, C = t->C;
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
   float* nat = t->d_nat;
-  const std::vector<float*> sp = state_table(t);
+  const std::vector<float*>& sp = t->sp;
+  const std::vector<int>& rots = t->rots;
   const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
   if (!sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
   // ---- forward (eval mode) ----
-  int rot = 0;
-  std::vector<int> rots(desc.n_ops + 1, 0);
   for (int i = 0; i < desc.n_ops; ++i) {
     const zf_op_desc& op = desc.ops[i];
-    rots[i] = rot;
+    if (op.kind == ZF_OP_ROLL) continue;  // an index rotation: rots[i + 1]
+    const int rot = rots[i];
     float* sin = sp[i];
     float* sout = sp[i + 1];
-    if (op.kind == ZF_OP_ROLL) {
-      rot = pmodi(rot - op.shift, D);
-    } else if (op.kind == ZF_OP_SHIFT_BOUNDS) {  // i == 0 (zf_trainer_create)
+    if (op.kind == ZF_OP_SHIFT_BOUNDS) {  // i == 0 (zf_trainer_create)
       hipLaunchKernelGGL(sb_eval_fwd_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sin, sout, t->d_ld,
                          (const float*)(nat + op.off_sb), B, D);
       ZF_CHECK_LAUNCH("sb_eval_fwd_kernel");
@@ -676,8 +697,8 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
   const LatentConsts lc(desc);
   float* g = t->d_g0;
   float* g_prev = t->d_g1;
-  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, cot, B, D, rot,
-                     lc.lt, lc.a, lc.betac, lc.tnm, lp_out, t->d_ce, g);
+  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, cot, B, D,
+                     rots[desc.n_ops], lc.lt, lc.a, lc.betac, lc.tnm, lp_out, t->d_ce, g);
   ZF_CHECK_LAUNCH("latent_vjp_kernel");
   if (!gx && !gc) return ZF_OK;
   // ---- reverse ----
@@ -715,10 +736,11 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
 
 // The whole step (body + optimiser) captured once per batch size; the
 // weighted step has a cache of its own, bounded the same way (weighted and
-// unweighted steps may alternate on one trainer).
-int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out, bool weighted = false) {
-  std::map<int64_t, hipGraphExec_t>& graphs = weighted ? t->graphs_w : t->graphs;
-  auto it = graphs.find(B);
+// unweighted steps may alternate on one trainer).  One device, no gc: the
+// graph reads only the trainer's own buffers, which the batch is staged into.
+int step_graph(zf_trainer_t* t, const BatchArgs& a, hipGraphExec_t* out) {
+  std::map<int64_t, hipGraphExec_t>& graphs = a.w ? t->graphs_w : t->graphs;
+  auto it = graphs.find(a.rows);
   if (it != graphs.end()) {
     *out = it->second;
     return ZF_OK;
@@ -726,13 +748,14 @@ int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out, bool weighted = fals
   if (graphs.size() >= 8) {  // bound the cache (batch sizes rarely vary)
     ZF_TRY_HIP(hipStreamSynchronize(t->cap));
     ZF_TRY_HIP(hipDeviceSynchronize());
-    for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
-    graphs.clear();
+    drop_graphs(graphs);
   }
   ZF_TRY_HIP(hipStreamBeginCapture(t->cap, hipStreamCaptureModeThreadLocal));
-  bool stepped = false;
-  int rc = trainer_body(t, B, B, 1, t->d_grad, t->cap, t->chain_on ? nullptr : &stepped, nullptr, weighted);
-  if (!rc) rc = trainer_update(t, t->cap, stepped);
+  BatchArgs b = a;
+  b.gc = nullptr;
+  b.stream = t->cap;
+  int rc = trainer_body(t, b, t->d_grad, !t->chain_on);
+  if (!rc) rc = trainer_update(t, t->cap, !t->chain_on);
   hipGraph_t g = nullptr;
   const hipError_t e = hipStreamEndCapture(t->cap, &g);
   if (!rc && e != hipSuccess) rc = hip_status(e, "hipStreamEndCapture");
@@ -743,9 +766,45 @@ int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out, bool weighted = fals
   }
   if (g) (void)hipGraphDestroy(g);
   if (rc) return rc;
-  graphs[B] = exec;
+  graphs[a.rows] = exec;
   *out = exec;
   return ZF_OK;
+}
+
+inline int copy_loss(zf_trainer_t* t, const BatchArgs& a) {
+  if (a.loss) ZF_TRY_HIP(hipMemcpyAsync(a.loss, loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, a.stream));
+  return ZF_OK;
+}
+
+// Every zf_trainer_loss_grad* entry: the loss and its gradient (and gc).
+int run_loss_grad(zf_trainer_t* t, const BatchArgs& a) {
+  int rc = check_batch(t, a);
+  if (!rc) rc = trainer_stage(t, a.x, a.c, a.w, a.rows, a.stream);
+  if (!rc) rc = trainer_body(t, a, a.grad ? a.grad : t->d_grad, false);
+  return rc ? rc : copy_loss(t, a);
+}
+
+// Every zf_trainer_step* entry (update_stats = 1, the gradient in d_grad).
+// The captured graph writes no gc and holds no collective: a step with gc,
+// or with a communicator, launches the same kernels in the same order
+// eagerly, so the same bits (tests/test_gpu_train.py::test_step_graph_matches_eager).
+int run_step(zf_trainer_t* t, const BatchArgs& a) {
+  int rc = check_batch(t, a);
+  if (!rc) rc = trainer_stage(t, a.x, a.c, a.w, a.rows, a.stream);
+  if (rc) return rc;
+  const bool one_device = t->comm.world == 1;
+  if (!(t->C > 0 && a.gc) && t->use_graph && one_device) {
+    hipGraphExec_t exec = nullptr;
+    if ((rc = step_graph(t, a, &exec))) return rc;
+    ZF_TRY_HIP(hipGraphLaunch(exec, a.stream));
+  } else {
+    const bool step_in_cast = !t->chain_on && one_device;
+    rc = trainer_body(t, a, t->d_grad, step_in_cast);
+    if (!rc) rc = trainer_update(t, a.stream, step_in_cast);
+    if (rc) return rc;
+  }
+  t->t += 1;
+  return copy_loss(t, a);
 }
 
 }  // namespace
@@ -753,131 +812,58 @@ int step_graph(zf_trainer_t* t, int B, hipGraphExec_t* out, bool weighted = fals
 
 extern "C" {
 
-int zf_trainer_loss_grad_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows,
-                               int update_stats, double* loss, float* grad, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  int rc = zf::trainer_stage(t, x, c, rows, st);
-  if (rc) return rc;
-  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
-  rc = zf::trainer_body(t, (int)rows, global_rows, update_stats, grad ? grad : t->d_grad, st);
-  if (rc) return rc;
-  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
-  return ZF_OK;
+// The eight loss_grad / step entries are views of run_loss_grad / run_step:
+// w == NULL is the unweighted loss, gc == NULL (or C == 0) writes no gc, and
+// the plain entries' global batch is B rows on every rank.
+int zf_trainer_loss_grad_weighted_shard(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t rows,
+                                        int64_t global_rows, int update_stats, double* loss, float* grad, float* gc,
+                                        void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  return zf::run_loss_grad(t, {x, c, w, rows, global_rows, update_stats, loss, grad, gc, (hipStream_t)stream});
 }
 
 int zf_trainer_loss_grad_cond_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows,
                                     int64_t global_rows, int update_stats, double* loss, float* grad, float* gc,
                                     void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  if (!gc || t->C == 0)
-    return zf_trainer_loss_grad_shard(t, x, c, rows, global_rows, update_stats, loss, grad, stream);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = zf::trainer_stage(t, x, c, rows, st);
-  if (rc) return rc;
-  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
-  rc = zf::trainer_body(t, (int)rows, global_rows, update_stats, grad ? grad : t->d_grad, st, nullptr, gc);
-  if (rc) return rc;
-  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
-  return ZF_OK;
+  return zf::run_loss_grad(t, {x, c, nullptr, rows, global_rows, update_stats, loss, grad, gc, (hipStream_t)stream});
+}
+
+int zf_trainer_loss_grad_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows,
+                               int update_stats, double* loss, float* grad, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  return zf::run_loss_grad(
+      t, {x, c, nullptr, rows, global_rows, update_stats, loss, grad, nullptr, (hipStream_t)stream});
 }
 
 int zf_trainer_loss_grad(zf_trainer_t* t, const float* x, const float* c, int64_t B, int update_stats,
                          double* loss, float* grad, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  return zf_trainer_loss_grad_shard(t, x, c, B, B * t->comm.world, update_stats, loss, grad, stream);
+  return zf::run_loss_grad(
+      t, {x, c, nullptr, B, B * t->comm.world, update_stats, loss, grad, nullptr, (hipStream_t)stream});
+}
+
+int zf_trainer_step_weighted_shard(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t rows,
+                                   int64_t global_rows, double* loss, float* gc, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  return zf::run_step(t, {x, c, w, rows, global_rows, 1, loss, nullptr, gc, (hipStream_t)stream});
+}
+
+int zf_trainer_step_cond_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows,
+                               double* loss, float* gc, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  return zf::run_step(t, {x, c, nullptr, rows, global_rows, 1, loss, nullptr, gc, (hipStream_t)stream});
 }
 
 int zf_trainer_step_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows,
                           double* loss, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  int rc = zf::trainer_stage(t, x, c, rows, st);
-  if (rc) return rc;
-  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
-  if (t->use_graph && t->comm.world == 1) {  // collectives are issued eagerly
-    hipGraphExec_t exec = nullptr;
-    rc = zf::step_graph(t, (int)rows, &exec);
-    if (rc) return rc;
-    ZF_TRY_HIP(hipGraphLaunch(exec, st));
-  } else {
-    bool stepped = false;
-    rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped);
-    if (!rc) rc = zf::trainer_update(t, st, stepped);
-    if (rc) return rc;
-  }
-  t->t += 1;
-  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
-  return ZF_OK;
+  if (!t) return zf::einval("trainer is NULL");
+  return zf::run_step(t, {x, c, nullptr, rows, global_rows, 1, loss, nullptr, nullptr, (hipStream_t)stream});
 }
 
-// With gc the step is launched eagerly (the captured step graph stays as it
-// is and writes no gc): the same kernels in the same order, so the same bits
-// (tests/test_gpu_train.py::test_step_graph_matches_eager).
-int zf_trainer_step_cond_shard(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows,
-                               double* loss, float* gc, void* stream) {
+int zf_trainer_step(zf_trainer_t* t, const float* x, const float* c, int64_t B, double* loss, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  if (!gc || t->C == 0) return zf_trainer_step_shard(t, x, c, rows, global_rows, loss, stream);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = zf::trainer_stage(t, x, c, rows, st);
-  if (rc) return rc;
-  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
-  bool stepped = false;
-  rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped, gc);
-  if (!rc) rc = zf::trainer_update(t, st, stepped);
-  if (rc) return rc;
-  t->t += 1;
-  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
-  return ZF_OK;
-}
-
-// Weighted maximum likelihood: loss = -sum_b w_b lp_b / sum_b w_b over the
-// global batch, w this rank's `rows` weights (trainer_body, weighted).
-int zf_trainer_loss_grad_weighted_shard(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t rows,
-                                        int64_t global_rows, int update_stats, double* loss, float* grad, float* gc,
-                                        void* stream) {
-  if (!t) return zf::einval("trainer is NULL");
-  if (!w) return zf_trainer_loss_grad_cond_shard(t, x, c, rows, global_rows, update_stats, loss, grad, gc, stream);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = zf::trainer_stage(t, x, c, rows, st, w);
-  if (rc) return rc;
-  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
-  rc = zf::trainer_body(t, (int)rows, global_rows, update_stats, grad ? grad : t->d_grad, st, nullptr, gc, true);
-  if (rc) return rc;
-  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
-  return ZF_OK;
-}
-
-// The weighted step replays its own captured graph per batch size (it reads
-// the staged weights at a fixed address); with gc, or a communicator, it is
-// launched eagerly, as zf_trainer_step_cond_shard is.
-int zf_trainer_step_weighted_shard(zf_trainer_t* t, const float* x, const float* c, const float* w, int64_t rows,
-                                   int64_t global_rows, double* loss, float* gc, void* stream) {
-  if (!t) return zf::einval("trainer is NULL");
-  if (!w) return zf_trainer_step_cond_shard(t, x, c, rows, global_rows, loss, gc, stream);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = zf::trainer_stage(t, x, c, rows, st, w);
-  if (rc) return rc;
-  if (global_rows < rows || (t->comm.world == 1 && global_rows != rows))
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
-  if (t->C == 0) gc = nullptr;
-  if (!gc && t->use_graph && t->comm.world == 1) {
-    hipGraphExec_t exec = nullptr;
-    rc = zf::step_graph(t, (int)rows, &exec, true);
-    if (rc) return rc;
-    ZF_TRY_HIP(hipGraphLaunch(exec, st));
-  } else {
-    bool stepped = false;
-    rc = zf::trainer_body(t, (int)rows, global_rows, 1, t->d_grad, st, t->chain_on ? nullptr : &stepped, gc, true);
-    if (!rc) rc = zf::trainer_update(t, st, stepped);
-    if (rc) return rc;
-  }
-  t->t += 1;
-  if (loss) ZF_TRY_HIP(hipMemcpyAsync(loss, zf::loss_slot(t), sizeof(double), hipMemcpyDeviceToDevice, st));
-  return ZF_OK;
+  return zf::run_step(t, {x, c, nullptr, B, B * t->comm.world, 1, loss, nullptr, nullptr, (hipStream_t)stream});
 }
 
 int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, const float* cot, float* log_prob,
@@ -897,11 +883,6 @@ int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, con
     if (rc) return rc;
   }
   return ZF_OK;
-}
-
-int zf_trainer_step(zf_trainer_t* t, const float* x, const float* c, int64_t B, double* loss, void* stream) {
-  if (!t) return zf::einval("trainer is NULL");
-  return zf_trainer_step_shard(t, x, c, B, B * t->comm.world, loss, stream);
 }
 
 int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
@@ -1046,10 +1027,8 @@ int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, con
   }
   ZF_TRY_HIP(hipStreamSynchronize(t->cap));
   ZF_TRY_HIP(hipDeviceSynchronize());
-  for (auto& kv : t->graphs) (void)hipGraphExecDestroy(kv.second);
-  t->graphs.clear();
-  for (auto& kv : t->graphs_w) (void)hipGraphExecDestroy(kv.second);
-  t->graphs_w.clear();
+  zf::drop_graphs(t->graphs);
+  zf::drop_graphs(t->graphs_w);
   zf::free_chain(t);
   const size_t need = (size_t)t->nat_floats;
   int rc = ZF_OK;

@@ -67,6 +67,10 @@ _F32_SUM_LIMIT = float(np.finfo(np.float32).max)
 DEFAULT_OPTIMIZER = nadamw  # train.py:13-16 (optax.nadamw when available)
 
 
+def _ptr(a: Optional[DeviceArray]) -> Optional[int]:
+    return None if a is None else a.ptr
+
+
 class Trainer:
     """Device-resident training state of one Flow: natural blob (params +
     batch statistics), gradient, optimiser moments, activation arena for
@@ -178,32 +182,32 @@ class Trainer:
         xd, cd = self._dev(x, self.D), self._dev(c, self.C)
         g = DeviceArray((self.program.blob.size,))
         rows = xd.shape[0]
-        if w is not None:
-            wd = self._weights(w, rows)
-            gc = self._gc_out(rows) if cond_grad else None
-            check(L.load_library().zf_trainer_loss_grad_weighted_shard(
-                self.handle, xd.ptr, None if cd is None else cd.ptr, wd.ptr, rows, self._global(rows, global_rows),
-                1 if update_stats else 0, self._loss.ptr, g.ptr, None if gc is None else gc.ptr, L.stream()),
-                "zf_trainer_loss_grad_weighted")
-            self._last_rows = None  # the weighted loss is the device's fp64 value as is
-            loss = float(self._loss.numpy()[0])
-            if cond_grad:
-                return loss, g.numpy(), (gc if isinstance(c, DeviceArray) else gc.numpy())
-            return loss, g.numpy()
-        if cond_grad:
-            gc = self._gc_out(rows)
-            check(L.load_library().zf_trainer_loss_grad_cond_shard(
-                self.handle, xd.ptr, cd.ptr, rows, self._global(rows, global_rows),
-                1 if update_stats else 0, self._loss.ptr, g.ptr, gc.ptr, L.stream()), "zf_trainer_loss_grad_cond")
-        else:
-            check(L.load_library().zf_trainer_loss_grad_shard(
-                self.handle, xd.ptr, None if cd is None else cd.ptr, rows, self._global(rows, global_rows),
-                1 if update_stats else 0, self._loss.ptr, g.ptr, L.stream()), "zf_trainer_loss_grad")
-        self._last_rows = self._global(rows, global_rows)
+        wd = None if w is None else self._weights(w, rows)
+        gc = self._gc_out(rows) if cond_grad else None
+        self._call_loss_grad(xd.ptr, _ptr(cd), _ptr(wd), rows, self._global(rows, global_rows), update_stats, g.ptr,
+                             _ptr(gc))
         loss = self._fp32_mean(float(self._loss.numpy()[0]))
         if cond_grad:
-            return loss, g.numpy(), (gc if isinstance(c, DeviceArray) else gc.numpy())
+            return loss, g.numpy(), self._gc_like(gc, c)
         return loss, g.numpy()
+
+    def _call_loss_grad(self, xptr, cptr, wptr, rows, global_rows, update_stats, gptr, gcptr) -> None:
+        """The one loss_grad call (``wptr`` / ``gcptr`` None: unweighted / no gc)."""
+        check(L.load_library().zf_trainer_loss_grad_weighted_shard(
+            self.handle, xptr, cptr, wptr, rows, global_rows, 1 if update_stats else 0, self._loss.ptr, gptr, gcptr,
+            L.stream()), "zf_trainer_loss_grad")
+        self._last_rows = None if wptr is not None else global_rows
+
+    def _call_step(self, xptr, cptr, wptr, rows, global_rows, gcptr) -> None:
+        """The one step call (async); a weighted loss is the device's fp64
+        value as is (``_last_rows`` None, see :meth:`_fp32_mean`)."""
+        check(L.load_library().zf_trainer_step_weighted_shard(
+            self.handle, xptr, cptr, wptr, rows, global_rows, self._loss.ptr, gcptr, L.stream()), "zf_trainer_step")
+        self._last_rows = None if wptr is not None else global_rows
+
+    @staticmethod
+    def _gc_like(gc: DeviceArray, c):
+        return gc if isinstance(c, DeviceArray) else gc.numpy()
 
     def _gc_out(self, rows: int) -> DeviceArray:
         if self.C == 0:
@@ -222,22 +226,9 @@ class Trainer:
         xd, cd = self._dev(x, self.D), self._dev(c, self.C)
         rows = xd.shape[0]
         wd = None if w is None else self._weights(w, rows)
-        if not cond_grad:
-            self._step_rows(xd.ptr, None if cd is None else cd.ptr, rows, global_rows,
-                            None if wd is None else wd.ptr)
-            return None
-        gc = self._gc_out(rows)
-        if wd is not None:
-            self._last_rows = None
-            check(L.load_library().zf_trainer_step_weighted_shard(
-                self.handle, xd.ptr, cd.ptr, wd.ptr, rows, self._global(rows, global_rows), self._loss.ptr, gc.ptr,
-                L.stream()), "zf_trainer_step_weighted")
-            return gc if isinstance(c, DeviceArray) else gc.numpy()
-        self._last_rows = self._global(rows, global_rows)
-        check(L.load_library().zf_trainer_step_cond_shard(self.handle, xd.ptr, cd.ptr, rows,
-                                                          self._global(rows, global_rows), self._loss.ptr, gc.ptr,
-                                                          L.stream()), "zf_trainer_step_cond")
-        return gc if isinstance(c, DeviceArray) else gc.numpy()
+        gc = self._gc_out(rows) if cond_grad else None
+        self._call_step(xd.ptr, _ptr(cd), _ptr(wd), rows, self._global(rows, global_rows), _ptr(gc))
+        return self._gc_like(gc, c) if cond_grad else None
 
     def log_prob_vjp(self, x: DeviceArray, c: Optional[DeviceArray] = None, cotangent: Optional[DeviceArray] = None):
         """Eval-mode ``(log_prob, dx, dc)`` at the trainer's current
@@ -261,15 +252,7 @@ class Trainer:
                    wptr: Optional[int] = None) -> None:
         """One step on ``rows`` device-resident rows (raw pointers; async);
         ``wptr``: their weights (the weighted loss)."""
-        if wptr is not None:
-            self._last_rows = None
-            check(L.load_library().zf_trainer_step_weighted_shard(
-                self.handle, xptr, cptr, wptr, rows, self._global(rows, global_rows), self._loss.ptr, None,
-                L.stream()), "zf_trainer_step_weighted")
-            return
-        self._last_rows = self._global(rows, global_rows)
-        check(L.load_library().zf_trainer_step_shard(self.handle, xptr, cptr, rows, self._global(rows, global_rows),
-                                                     self._loss.ptr, L.stream()), "zf_trainer_step")
+        self._call_step(xptr, cptr, wptr, rows, self._global(rows, global_rows), None)
 
     def _step_local(self, xptr: int, cptr: Optional[int], rows: int, wptr: Optional[int] = None) -> None:
         """One step on the whole batch without the cross-rank reductions:
@@ -279,14 +262,7 @@ class Trainer:
         if self.world > 1:
             check(lib.zf_trainer_set_comm(self.handle, None), "zf_trainer_set_comm")
         try:
-            if wptr is not None:
-                self._last_rows = None
-                check(lib.zf_trainer_step_weighted_shard(self.handle, xptr, cptr, wptr, rows, rows, self._loss.ptr,
-                                                         None, L.stream()), "zf_trainer_step_weighted")
-            else:
-                self._last_rows = rows
-                check(lib.zf_trainer_step_shard(self.handle, xptr, cptr, rows, rows, self._loss.ptr, L.stream()),
-                      "zf_trainer_step")
+            self._call_step(xptr, cptr, wptr, rows, rows, None)
         finally:
             if self.world > 1:
                 check(lib.zf_trainer_set_comm(self.handle, ct.byref(self._comm_desc)), "zf_trainer_set_comm")
