@@ -69,7 +69,13 @@ int zf_stream_wait_event(void* stream, void* event);
 /* Replaces utils.rational_quadratic_spline_forward (src/zenflow/utils.py:65-141).
  * x (M,N), dx/dy (M,N,K) normalised widths/heights, slope (M,N,K-1) inner knot
  * derivatives -> y (M,N), log_det (M,) = sum over N of log dy/dx.
- * y and/or log_det may be NULL. */
+ * y and/or log_det may be NULL.
+ * Shape limits (both directions): M >= 0, N >= 1, 1 <= K <= 256, else
+ * ZF_EINVAL.  One block holds whole rows: K in {4, 8, 16, 32} with 16-byte
+ * aligned dx and dy takes N <= 256; every other K or alignment stages its rows
+ * through 48 KiB of LDS and needs N <= 256 and N * (3 * ks + 1) <= 12288 with
+ * ks = K + 1 (K even) or K + 2 (K odd), i.e. roughly N * (3K + 4) floats —
+ * beyond that ZF_ENOTSUP. */
 int zf_rqs_forward(const float* x, const float* dx, const float* dy, const float* slope,
                    float* y, float* log_det, int64_t M, int N, int K, void* stream);
 
@@ -80,12 +86,15 @@ int zf_rqs_inverse(const float* y, const float* dx, const float* dy, const float
 /* Replaces utils.squareplus (src/zenflow/utils.py:18-20), elementwise, b = 4 by default. */
 int zf_squareplus(const float* x, float* y, int64_t n, float b, void* stream);
 
-/* Replaces utils.softmax_with_threshold (src/zenflow/utils.py:23-34) over rows of K. */
+/* Replaces utils.softmax_with_threshold (src/zenflow/utils.py:23-34) over rows of K.
+ * 1 <= K <= 6144 (one row, at an odd stride, within 48 KiB of LDS), else ZF_EINVAL. */
 int zf_softmax_with_threshold(const float* x, float* y, int64_t M, int K, double threshold,
                               void* stream);
 
 /* Replaces utils.normalize_spline_params (src/zenflow/utils.py:37-62):
- * raw (M, K) / (M, K) / (M, K-1) logits -> normalised, written in place. */
+ * raw (M, K) / (M, K) / (M, K-1) logits -> normalised, written in place.
+ * 1 <= K <= 6143 (a dx and a dy row, each at an odd stride, within 48 KiB of
+ * LDS), else ZF_EINVAL; slope may be NULL at K = 1. */
 int zf_normalize_spline_params(float* dx, float* dy, float* slope, int64_t M, int K,
                                void* stream);
 

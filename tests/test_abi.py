@@ -1,6 +1,7 @@
 """The C-ABI library loads on a CPU-only host and exports every symbol that
 include/zenflow_amd.h declares; host-only entry points (planning, error
-reporting) behave.  No GPU compute is called here."""
+reporting) behave, and the standalone entries reject bad arguments before
+their first HIP call.  No GPU compute is called here."""
 
 import ctypes
 import re
@@ -127,3 +128,103 @@ def test_header_constants_match_python():
     assert len(mirrored) >= 20, mirrored
     for n in mirrored:
         assert getattr(L, n) == int(defs[n]), n
+
+
+# ---------------------------------------------------------------------------
+# Argument validation of the standalone entries: every check below returns
+# before the first HIP call, so host pointers stand in for device ones.
+# ---------------------------------------------------------------------------
+
+
+def _host_ptr():
+    buf = np.zeros(64, np.float32)
+    return buf, buf.ctypes.data
+
+
+def _rejected(rc, want):
+    from zenflow_amd import _lib as L
+
+    assert rc == want
+    assert L.load_library().zf_last_error()
+
+
+@pytest.mark.parametrize("K", [6144, 6145, 0])
+def test_normalize_spline_params_rejects_k(K):
+    """K = 6144 passes the K <= 6144 gate but leaves no room for one dx and one
+    dy row (2 * 6145 floats > 12288): an error, not a division by zero rows."""
+    from zenflow_amd import _lib as L
+
+    buf, p = _host_ptr()
+    _rejected(L.load_library().zf_normalize_spline_params(p, p, p, 3, K, None), -1)
+
+
+@pytest.mark.parametrize("K", [6145, 0])
+def test_softmax_with_threshold_rejects_k(K):
+    from zenflow_amd import _lib as L
+
+    buf, p = _host_ptr()
+    _rejected(L.load_library().zf_softmax_with_threshold(p, p, 3, K, 1e-5, None), -1)
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize(
+    "M,N,K,rc",
+    [
+        (4, 2, 257, -1),
+        (4, 2, 0, -1),
+        (4, 0, 16, -1),
+        (-1, 2, 16, -1),
+        (4, 257, 16, -2),  # more items than one block's threads
+        (4, 64, 64, -2),  # 64 * (3 * 65 + 1) = 12544 floats > 12288
+        (4, 17, 255, -2),  # 17 * (3 * 257 + 1) = 13124
+        (4, 256, 15, -2),  # 256 * (3 * 17 + 1) = 13312
+    ],
+)
+def test_rqs_rejects_shapes(inverse, M, N, K, rc):
+    from zenflow_amd import _lib as L
+
+    lib = L.load_library()
+    buf, p = _host_ptr()
+    if inverse:
+        got = lib.zf_rqs_inverse(p, p, p, p, p, M, N, K, None)
+    else:
+        got = lib.zf_rqs_forward(p, p, p, p, p, p, M, N, K, None)
+    _rejected(got, rc)
+
+
+@pytest.mark.parametrize(
+    "N,ncols,ld,off,ws",
+    [
+        (8, 0, 4, 0, True),
+        (8, 65, 70, 0, True),
+        (8, 3, 4, 2, True),  # ld < ncols + col_offset
+        (8, 3, 8, -1, True),
+        (-1, 3, 3, 0, True),
+        (8, 3, 3, 0, False),  # NULL workspace
+    ],
+)
+def test_colstats_rejects(N, ncols, ld, off, ws):
+    from zenflow_amd import _lib as L
+
+    buf, p = _host_ptr()
+    rc = L.load_library().zf_colstats(p, N, ncols, ld, off, None, None, p, p, p, p, p if ws else None, None)
+    _rejected(rc, -1)
+
+
+@pytest.mark.parametrize(
+    "latent,param,N,D",
+    [
+        (0, 0.0, 4, 2),  # ZF_LATENT_NONE is not a distribution
+        (5, 0.0, 4, 2),
+        (-1, 0.0, 4, 2),
+        (2, 0.5, 4, 2),  # Beta peakness < 1
+        (2, float("nan"), 4, 2),
+        (1, 0.0, 4, 0),
+        (1, 0.0, -1, 2),
+    ],
+)
+def test_latent_sample_rejects(latent, param, N, D):
+    from zenflow_amd import _lib as L
+
+    buf, p = _host_ptr()
+    _rejected(L.load_library().zf_latent_sample(latent, param, 7, p, N, D, None), -1)

@@ -446,11 +446,19 @@ __global__ __launch_bounds__(256) void normalize_vec_kernel(float* __restrict__ 
   }
 }
 
-// utils.py:18-20 elementwise; b is the reference's `b` argument.
+// utils.py:18-20 elementwise; b is the reference's `b` argument.  x^2 and
+// x^2 + b round separately, as the reference's float32 ops do: x + sqrt(..)
+// cancels at large negative x, and for b < 4 the single rounding of a
+// contracted fma moves the result by more than 1e-5 of it.
 __global__ void squareplus_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n,
                                   float b) {
+#pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { const float v = x[i]; y[i] = 0.5f * (v + __builtin_sqrtf(v * v + b)); }
+  if (i < n) {
+    const float v = x[i];
+    const float sq = v * v;
+    y[i] = 0.5f * (v + __builtin_sqrtf(sq + b));
+  }
 }
 
 // utils.py:23-34 over rows of K; c and 1 + c*n are float64 Python scalars.
@@ -599,7 +607,10 @@ int zf_normalize_spline_params(float* dx, float* dy, float* slope, int64_t M, in
     ZF_CHECK_LAUNCH("normalize_vec_kernel");
     return ZF_OK;
   }
-  const int R = zf::rows_per_block(2 * K + 1);  // dx and dy rows share the LDS budget
+  // dx and dy rows share the LDS budget: R rows of each, at the stride the kernel lays them out with
+  int R = zf::kRowLdsFloats / (2 * zf::row_stride(K));
+  if (R > zf::kRowThreads) R = zf::kRowThreads;
+  if (R < 1) return zf::einval("K too large");
   const int64_t grid = (M + R - 1) / R;
   if (grid > 0x7fffffffLL) return zf::einval("M too large");
   hipLaunchKernelGGL(zf::normalize_kernel, dim3((unsigned)grid), dim3(zf::kRowThreads),

@@ -4,8 +4,9 @@
 ``log_prob`` runs on the GPU (the same latent epilogue the fused flow kernel
 uses).  ``sample`` draws on the GPU too (``zf_latent_sample``: Philox4x32-10
 keyed by the seed, counter = (row, dim), zf_random.h): JAX's threefry stream
-is not reproducible without JAX, so sampling parity is statistical (KS tests,
-moments), as the reference tests check it."""
+is not reproducible without JAX, so sampling parity with JAX is statistical (KS
+tests, moments), as the reference tests check it, while the device stream
+itself is pinned to its host restatement, tests/sampler_oracle.py."""
 
 from __future__ import annotations
 

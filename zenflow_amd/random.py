@@ -3,7 +3,8 @@
 JAX's threefry stream cannot be reproduced without JAX: parameter init uses
 seeded numpy Generators, latent sampling the device's counter-based Philox
 generator keyed by ``key_to_seed(key)`` — same distributions, different draws
-(parity for sampling is statistical; DESIGN.md §2 sampling)."""
+(parity with JAX is statistical; the device stream itself is pinned to its
+host restatement, tests/sampler_oracle.py; DESIGN.md §2 sampling)."""
 
 from __future__ import annotations
 
