@@ -427,6 +427,66 @@ int zf_trainer_step_weighted_shard(zf_trainer_t* trainer, const float* x, const 
 int zf_trainer_log_prob_vjp(zf_trainer_t* trainer, const float* x, const float* c, const float* cot,
                             float* log_prob, float* gx, float* gc, int64_t N, void* stream);
 
+/* Custom losses.  With the reference the loss is ordinary user code:
+ * flow.apply (flow.py:22-48) is a differentiable JAX function and the
+ * eighteen lines of train.py:64-86 (loss_fn, jax.grad, the optax update) are
+ * what users copy and change — a mixture with an analytic background,
+ * importance-weighted or penalised objectives, two flows under one loss,
+ * fine-tuning with frozen statistics, accumulated or edited gradients.  Every
+ * such loss L(lp_0 .. lp_{B-1}) of the per-row log_prob needs three steps,
+ * and these are the three entries:
+ *
+ * zf_trainer_forward: stages this rank's rows x (rows,D), c (rows,C) or NULL
+ *   (rows <= batch_max; global_rows as in the _shard entries) and runs the
+ *   forward pass, every activation the reverse pass reads kept in the
+ *   trainer.  log_prob (rows,) on the device receives lp with flow.py:47's
+ *   nan_to_num.
+ *     train != 0  flow.apply(..., train=True): the forward half of
+ *                 zf_trainer_loss_grad_shard — batch statistics, exchanged
+ *                 over the communicator, and the running-statistics update
+ *                 when update_stats != 0 (the same bits as that entry's).
+ *     train == 0  flow.apply(..., train=False): the forward of
+ *                 zf_trainer_log_prob_vjp (the same log_prob bits) on the
+ *                 stored statistics; nothing is exchanged; update_stats must
+ *                 be 0 (ZF_EINVAL, nothing enqueued).
+ *   The pass stays pending until zf_trainer_backward takes it.  Any of
+ *   loss_grad*, step*, log_prob_vjp, set_blob, set_optim_chain,
+ *   apply_gradient or another forward drops it.
+ *
+ * zf_trainer_backward: cot (rows,) fp32 on the device is d L / d lp_b of this
+ *   rank's rows (NULL: ones).  grad (blob layout, fp32, device; NULL: the
+ *   trainer's own gradient buffer, which the optimiser reads) receives
+ *     d / d blob of  sum over the GLOBAL batch of cot_b * nan_to_num(lp_b),
+ *   zero on the statistics entries and identical on every rank.  gc (rows,C)
+ *   or NULL receives d / d c of the same sum for this rank's rows,
+ *   accumulated in the order of the _cond_ entries.
+ *     - Rows whose lp is not finite before nan_to_num get cotangent 0 and
+ *       contribute exact zeros (the `where` gradient of nan_to_num).
+ *     - Eval mode: rows with cot == 0 contribute exact zeros.  Train mode:
+ *       they still enter through the batch statistics, as zero-weight rows of
+ *       the weighted loss do.
+ *     - Train mode is the reverse half of the weighted loss_grad with cot in
+ *       place of -w_b / Wsum: BatchNorm's reverse with its global sums, the
+ *       fp64 gradient shares gathered over the ranks.  Eval mode reverses
+ *       BatchNorm through the stored statistics (no batch term), forms the
+ *       scale / bias gradients from the column sums of gUbn * Uhat and gUbn
+ *       over the same leaf tree, and exchanges only the final gradient.
+ *   Needs a pending forward (ZF_EINVAL "no forward pending", nothing
+ *   enqueued); one backward per forward.
+ *
+ * zf_trainer_apply_gradient: the optimiser half of a step on grad (device,
+ *   blob layout; NULL: the trainer's own buffer) — the (n)adamw update or the
+ *   chain of zf_trainer_set_optim_chain; the step counter, the schedule and
+ *   the moments advance as in zf_trainer_step.  It does not communicate:
+ *   every rank passes the same gradient, which is what backward returns.
+ *
+ * All three launch eagerly on `stream`; the captured step graphs are the
+ * zf_trainer_step* entries' alone. */
+int zf_trainer_forward(zf_trainer_t* trainer, const float* x, const float* c, int64_t rows, int64_t global_rows,
+                       int train, int update_stats, float* log_prob, void* stream);
+int zf_trainer_backward(zf_trainer_t* trainer, const float* cot, float* grad, float* gc, void* stream);
+int zf_trainer_apply_gradient(zf_trainer_t* trainer, const float* grad, void* stream);
+
 /* Copy the trainer's natural blob (parameters + statistics) out / in. */
 int zf_trainer_get_blob(zf_trainer_t* trainer, float* blob_host);
 int zf_trainer_set_blob(zf_trainer_t* trainer, const float* blob_host);

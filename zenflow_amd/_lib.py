@@ -182,6 +182,9 @@ SIGNATURES = {
     "zf_trainer_loss_grad_weighted_shard": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "zf_trainer_step_weighted_shard": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "zf_trainer_log_prob_vjp": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "zf_trainer_forward": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
+    "zf_trainer_backward": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "zf_trainer_apply_gradient": (_int, [_vp, _vp, _vp]),
     "zf_trainer_get_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_optim_chain": (_int, [_vp, _vp, _vp]),

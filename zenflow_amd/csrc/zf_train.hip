@@ -105,10 +105,16 @@ struct zf_trainer {
     float *mean, *rstd;
   };
   std::vector<NscBufs> nsc;
+  // zf_trainer_forward's pass, waiting for its zf_trainer_backward (kPend*)
+  int pend_mode = 0;
+  int64_t pend_rows = 0, pend_global = 0;
 };
 
 namespace zf {
 namespace {
+
+// zf_trainer::pend_mode: no forward pending, or the mode zf_trainer_forward ran in
+enum { kPendNone = 0, kPendTrain = 1, kPendEval = 2 };
 
 float* dmalloc(zf_trainer* t, int64_t n, int& rc) {
   if (rc) return nullptr;
@@ -413,31 +419,16 @@ struct DgradChain {
 };
 
 
-// Train-mode forward + loss + reverse pass from the staged batch of B rows
-// (this rank's shard of a global batch of Bg rows); the loss lands in
-// loss_slot(t), the gradient in G (natural blob layout, fp32).
-// step_in_cast (one device, an (n)adamw update follows): the gradient cast also
-// advances the optimiser's step counter, and trainer_update skips step_kernel.
-// a.gc (this rank's (B, C) rows, or NULL): also d loss / d c, the condition
-// columns of every coupling's d loss / d U (train.py:64-86 differentiated
-// with respect to the conditions, as jax.grad(loss_fn_2) of
-// examples/deep_set.ipynb does through DeepSetFlow's c = phi(x)).  It only
-// adds stores: loss, G and the stepped blob keep their bits.
-// a.w != NULL: the loss is -sum_b w_b lp_b / sum_b w_b with the staged weights
-// d_w (the user's loss around flow.apply(..., train=True) for weighted
-// samples).  The weights enter at the loss only: the forward pass and its
-// batch statistics are the unweighted ones, and the reverse pass is seeded
-// with the per-row cotangent d_ce in place of the constant gl.
-int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cast) {
-  const int D = t->D, C = t->C, W = t->comm.world, B = (int)a.rows, update_stats = a.update_stats;
-  const long long Bg = a.global_rows;
-  hipStream_t st = a.stream;
-  float* const gc = C > 0 ? a.gc : nullptr;
-  const bool weighted = a.w != nullptr;
+// The train-mode forward of the staged batch of B rows (this rank's shard of a
+// global batch of Bg rows): batch statistics (exchanged over the ranks), the
+// running-statistics update when update_stats is set, every activation the
+// reverse pass reads kept in the arena, the log-det in d_ld.  The first half
+// of trainer_body and of zf_trainer_forward(train = 1).
+int trainer_forward_train(zf_trainer_t* t, int B, long long Bg, int update_stats, hipStream_t st) {
+  const int D = t->D, C = t->C, W = t->comm.world;
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
   float* nat = t->d_nat;
-  double* G64 = t->d_g64;
   const std::vector<int>& rots = t->rots;
   auto state = [&](int i) { return t->sp[i]; };
   // a leading ShiftBounds sets ld itself (sb_forward_kernel, first)
@@ -503,11 +494,47 @@ int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cas
       return zf::einval("op %d: unknown kind", i);
     }
   }
-  const int rot = rots[desc.n_ops];
+  return ZF_OK;
+}
+
+// How trainer_reverse seeds and closes the reverse pass.
+struct ReverseArgs {
+  bool rowce;         // d / d log_det of row b is d_ce[b] (else -1 / Bg for every row)
+  bool eval;          // the forward ran on the stored statistics (zf_trainer_forward, train = 0)
+  float* gc;          // this rank's (B, C) rows of d / d c, or NULL
+  float* G;           // the fp32 gradient (blob layout)
+  bool step_in_cast;  // one device, an (n)adamw update follows: the cast also steps
+};
+int trainer_reverse(zf_trainer_t* t, int B, long long Bg, const ReverseArgs& ra, hipStream_t st);
+
+// Train-mode forward + loss + reverse pass from the staged batch of B rows
+// (this rank's shard of a global batch of Bg rows); the loss lands in
+// loss_slot(t), the gradient in G (natural blob layout, fp32).
+// step_in_cast (one device, an (n)adamw update follows): the gradient cast also
+// advances the optimiser's step counter, and trainer_update skips step_kernel.
+// a.gc (this rank's (B, C) rows, or NULL): also d loss / d c, the condition
+// columns of every coupling's d loss / d U (train.py:64-86 differentiated
+// with respect to the conditions, as jax.grad(loss_fn_2) of
+// examples/deep_set.ipynb does through DeepSetFlow's c = phi(x)).  It only
+// adds stores: loss, G and the stepped blob keep their bits.
+// a.w != NULL: the loss is -sum_b w_b lp_b / sum_b w_b with the staged weights
+// d_w (the user's loss around flow.apply(..., train=True) for weighted
+// samples).  The weights enter at the loss only: the forward pass and its
+// batch statistics are the unweighted ones, and the reverse pass is seeded
+// with the per-row cotangent d_ce in place of the constant gl.
+int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cast) {
+  const int D = t->D, W = t->comm.world, B = (int)a.rows;
+  const long long Bg = a.global_rows;
+  hipStream_t st = a.stream;
+  const bool weighted = a.w != nullptr;
+  const zf_flow_desc& desc = t->desc;
+  auto state = [&](int i) { return t->sp[i]; };
+  int rc;
+  if ((rc = trainer_forward_train(t, B, Bg, a.update_stats, st))) return rc;
+  const int rot = t->rots[desc.n_ops];
   // ---- latent + loss ----
   const LatentConsts lc(desc);
-  float* g = t->d_g0;
-  float* g_prev = t->d_g1;
+  float* g = t->d_g0;  // d loss / d latent: where trainer_reverse starts
   {
     const Leaves ll = leaves_for(B, Bg, W, kLeafCap);
     // leaves that tile the 256-row blocks are summed inside the loss kernel
@@ -538,6 +565,32 @@ int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cas
     if ((rc = launch_tree_cols(t->d_leaf, ll.n, 1, loss_slot(t), st, t->d_leaf2))) return rc;
     if ((rc = dp_combine(t, loss_slot(t), 1, st))) return rc;
   }
+  return trainer_reverse(t, B, Bg, {weighted, false, a.gc, G, step_in_cast}, st);
+}
+
+// The reverse pass from d_g0 = d / d latent (and d_ce with ra.rowce) through
+// the activations a forward left in the arena, to the fp32 gradient ra.G: the
+// second half of trainer_body and of zf_trainer_backward.  ra.eval (the
+// forward ran on the stored statistics, nb.Uhat kept): the same spline
+// reverse, input-gradient GEMMs and deferred weight-gradient GEMMs; the
+// BatchNorm scale / bias gradients from the same leaf tree; the reverse
+// through BatchNorm without its batch terms (bn_eval_bwd_kernel), so only the
+// gradient gather at the end exchanges anything over the ranks.
+int trainer_reverse(zf_trainer_t* t, int B, long long Bg, const ReverseArgs& ra, hipStream_t st) {
+  const int D = t->D, C = t->C, W = t->comm.world;
+  float* const gc = C > 0 ? ra.gc : nullptr;
+  float* const G = ra.G;
+  const bool weighted = ra.rowce, step_in_cast = ra.step_in_cast;
+  const zf_flow_desc& desc = t->desc;
+  float* nat = t->d_nat;
+  double* G64 = t->d_g64;
+  const std::vector<int>& rots = t->rots;
+  auto state = [&](int i) { return t->sp[i]; };
+  const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
+  const bool small_ok = W == 1 && t->bn_small && !ra.eval;
+  float* g = t->d_g0;
+  float* g_prev = t->d_g1;
+  int rc;
   // ---- reverse ----
   // G64 needs no clearing per step: every parameter entry is assigned below
   // (the weight-gradient trees, the BatchNorm scale / bias gradients) and the
@@ -581,6 +634,19 @@ int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cas
       hipLaunchKernelGGL(zf::bn_bwd_small, dim3(1), dim3(1024), 0, st, nb.gU, nb.Uhat, bn + 2 * DC, nb.rstd,
                          gbn + 2 * DC, gbn + 3 * DC, g_prev, B, D, C, dt, dc, r, lbn.n, lbn.rows, gc, gc_assign);
       ZF_CHECK_LAUNCH("bn_bwd_small");
+    } else if (ra.eval) {
+      // scale / bias gradients: this rank's share of the sums of gUbn * Uhat
+      // and gUbn (rows with ce == 0 hold zeros), then gU = gUbn scale rstd
+      hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, nb.gU,
+                         nb.Uhat, B, DC, lbn.rows, lbn.n, t->d_leaf);
+      ZF_CHECK_LAUNCH("leaf_colsums_kernel");
+      if ((rc = launch_tree_cols(t->d_leaf, lbn.n, 2 * DC, t->d_roots, st, t->d_leaf2))) return rc;
+      ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, t->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+      ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, t->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
+                         (const float*)(bn + 2 * DC), (const float*)nb.rstd, (const float*)t->d_ce, g_prev, gc,
+                         gc_assign, B, D, C, dt, dc, r);
+      ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
     } else {
       // sums of gUbn and gUbn * Uhat: leaves -> tree (this rank's share of the
       // scale / bias gradient) -> (ranks) -> the reverse formula's global sums
@@ -651,16 +717,12 @@ int trainer_update(zf_trainer_t* t, hipStream_t st, bool step_done = false) {
   return ZF_OK;
 }
 
-// Eval-mode forward with stored activations and the reverse pass for one
-// chunk of B <= bmax rows (zf_trainer_log_prob_vjp): the trainer's GEMMs and
-// spline kernels, none of its batch reductions, weight-gradient GEMMs, fp64
-// accumulators or optimiser.  The GEMM forms follow the chunk's row count
-// (never the other rows' values): a row's bits depend on its own inputs and
-// on how many rows share the chunk only.
-int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const float* cot, float* lp_out, float* gx,
-                      float* gc, int B, hipStream_t st) {
-  int rc = trainer_stage(t, x, c_in, nullptr, B, st);  // checked by zf_trainer_log_prob_vjp
-  if (rc) return rc;
+// The eval-mode forward of the staged batch of B rows (BatchNorm on the stored
+// mean / var, ShiftBounds on the stored bounds: rows are independent, nothing
+// is exchanged), activations kept in the arena, the log-det in d_ld.  Bg picks
+// the GEMM forms.  keep_uhat: also every coupling's nb.Uhat, which the
+// BatchNorm scale gradient reads (zf_trainer_forward; Ubn has the same bits).
+int trainer_forward_eval(zf_trainer_t* t, int B, long long Bg, bool keep_uhat, hipStream_t st) {
   const int D = t->D, C = t->C;
   const float* c = t->d_c;
   const zf_flow_desc& desc = t->desc;
@@ -669,7 +731,7 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
   const std::vector<int>& rots = t->rots;
   const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
   if (!sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
-  // ---- forward (eval mode) ----
+  int rc;
   for (int i = 0; i < desc.n_ops; ++i) {
     const zf_op_desc& op = desc.ops[i];
     if (op.kind == ZF_OP_ROLL) continue;  // an index rotation: rots[i + 1]
@@ -684,15 +746,41 @@ int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const 
       int dt, dc, DC, S;
       nsc_dims(t, op, dt, dc, DC, S);
       zf_trainer::NscBufs& nb = t->nsc[i];
-      hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
-                         (const float*)(nat + op.off_bn), nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
-      ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
-      if ((rc = nsc_dense_fwd(t, op, nb, B, B, DC, dt * S, st))) return rc;
+      if (keep_uhat) {
+        hipLaunchKernelGGL(bn_eval_fwd_uhat_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
+                           (const float*)(nat + op.off_bn), nb.Uhat, nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
+        ZF_CHECK_LAUNCH("bn_eval_fwd_uhat_kernel");
+      } else {
+        hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
+                           (const float*)(nat + op.off_bn), nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
+        ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
+      }
+      if ((rc = nsc_dense_fwd(t, op, nb, Bg, B, DC, dt * S, st))) return rc;
       if ((rc = spline_fwd_launch(sin, sout, nb.P, t->d_ld, B, D, dt, op.knots, rot, st))) return rc;
     } else {
       return einval("op %d: unknown kind", i);
     }
   }
+  return ZF_OK;
+}
+
+// Eval-mode forward with stored activations and the reverse pass for one
+// chunk of B <= bmax rows (zf_trainer_log_prob_vjp): the trainer's GEMMs and
+// spline kernels, none of its batch reductions, weight-gradient GEMMs, fp64
+// accumulators or optimiser.  The GEMM forms follow the chunk's row count
+// (never the other rows' values): a row's bits depend on its own inputs and
+// on how many rows share the chunk only.
+int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const float* cot, float* lp_out, float* gx,
+                      float* gc, int B, hipStream_t st) {
+  int rc = trainer_stage(t, x, c_in, nullptr, B, st);  // checked by zf_trainer_log_prob_vjp
+  if (rc) return rc;
+  const int D = t->D, C = t->C;
+  const zf_flow_desc& desc = t->desc;
+  float* nat = t->d_nat;
+  const std::vector<float*>& sp = t->sp;
+  const std::vector<int>& rots = t->rots;
+  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
+  if ((rc = trainer_forward_eval(t, B, B, false, st))) return rc;
   // ---- latent, log_prob, the per-row cotangent ----
   const LatentConsts lc(desc);
   float* g = t->d_g0;
@@ -778,6 +866,7 @@ inline int copy_loss(zf_trainer_t* t, const BatchArgs& a) {
 
 // Every zf_trainer_loss_grad* entry: the loss and its gradient (and gc).
 int run_loss_grad(zf_trainer_t* t, const BatchArgs& a) {
+  t->pend_mode = kPendNone;  // the arena is about to be overwritten
   int rc = check_batch(t, a);
   if (!rc) rc = trainer_stage(t, a.x, a.c, a.w, a.rows, a.stream);
   if (!rc) rc = trainer_body(t, a, a.grad ? a.grad : t->d_grad, false);
@@ -789,6 +878,7 @@ int run_loss_grad(zf_trainer_t* t, const BatchArgs& a) {
 // or with a communicator, launches the same kernels in the same order
 // eagerly, so the same bits (tests/test_gpu_train.py::test_step_graph_matches_eager).
 int run_step(zf_trainer_t* t, const BatchArgs& a) {
+  t->pend_mode = kPendNone;
   int rc = check_batch(t, a);
   if (!rc) rc = trainer_stage(t, a.x, a.c, a.w, a.rows, a.stream);
   if (rc) return rc;
@@ -869,6 +959,7 @@ int zf_trainer_step(zf_trainer_t* t, const float* x, const float* c, int64_t B, 
 int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, const float* cot, float* log_prob,
                             float* gx, float* gc, int64_t N, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
+  t->pend_mode = zf::kPendNone;
   if (N < 1) return zf::einval("N must be at least 1");
   if (!x) return zf::einval("x is NULL");
   if (t->C > 0 && !c) return zf::einval("flow is conditional but c is NULL");
@@ -885,6 +976,65 @@ int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, con
   return ZF_OK;
 }
 
+// ---- custom losses: forward, backward(cotangent), apply_gradient ----
+// The user's loss around flow.apply (train.py:64-86, flow.py:22-48) is host
+// code between two calls: forward hands out the per-row log_prob, backward
+// takes d loss / d log_prob per row and returns the parameter gradient.
+int zf_trainer_forward(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows, int train,
+                       int update_stats, float* log_prob, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  t->pend_mode = zf::kPendNone;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc0 = zf::check_batch(t, {x, c, nullptr, rows, global_rows, update_stats, nullptr, nullptr, nullptr, st});
+  if (rc0) return rc0;
+  if (!log_prob) return zf::einval("log_prob is NULL");
+  if (!train && update_stats) return zf::einval("update_stats needs train mode (eval mode reads the stored statistics)");
+  if (t->desc.latent == ZF_LATENT_NONE) return zf::einval("flow has no latent distribution");
+  const int B = (int)rows;
+  int rc = zf::trainer_stage(t, x, c, nullptr, rows, st);
+  if (!rc)
+    rc = train ? zf::trainer_forward_train(t, B, global_rows, update_stats, st)
+               : zf::trainer_forward_eval(t, B, global_rows, true, st);
+  if (rc) return rc;
+  // log_prob with nan_to_num; its ce / gz outputs are rewritten by backward's launch
+  const zf::LatentConsts lc(t->desc);
+  hipLaunchKernelGGL(zf::latent_vjp_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, t->sp[t->n_ops], t->d_ld,
+                     (const float*)nullptr, B, t->D, t->rots[t->n_ops], lc.lt, lc.a, lc.betac, lc.tnm, log_prob,
+                     t->d_ce, t->d_g0);
+  ZF_CHECK_LAUNCH("latent_vjp_kernel");
+  t->pend_mode = train ? zf::kPendTrain : zf::kPendEval;
+  t->pend_rows = rows;
+  t->pend_global = global_rows;
+  return ZF_OK;
+}
+
+int zf_trainer_backward(zf_trainer_t* t, const float* cot, float* grad, float* gc, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (t->pend_mode == zf::kPendNone) return zf::einval("no forward pending");
+  const bool eval = t->pend_mode == zf::kPendEval;
+  t->pend_mode = zf::kPendNone;  // one backward per forward
+  hipStream_t st = (hipStream_t)stream;
+  const int B = (int)t->pend_rows;
+  // ce = cot where log_prob is finite before nan_to_num (0 elsewhere), gz = ce . d latent_lp / dz
+  const zf::LatentConsts lc(t->desc);
+  hipLaunchKernelGGL(zf::latent_vjp_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, t->sp[t->n_ops], t->d_ld, cot,
+                     B, t->D, t->rots[t->n_ops], lc.lt, lc.a, lc.betac, lc.tnm, (float*)nullptr, t->d_ce, t->d_g0);
+  ZF_CHECK_LAUNCH("latent_vjp_kernel");
+  return zf::trainer_reverse(t, B, t->pend_global, {true, eval, gc, grad ? grad : t->d_grad, false}, st);
+}
+
+int zf_trainer_apply_gradient(zf_trainer_t* t, const float* grad, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  t->pend_mode = zf::kPendNone;
+  hipStream_t st = (hipStream_t)stream;
+  if (grad && grad != t->d_grad)
+    ZF_TRY_HIP(hipMemcpyAsync(t->d_grad, grad, (size_t)t->nat_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
+  const int rc = zf::trainer_update(t, st);
+  if (rc) return rc;
+  t->t += 1;
+  return ZF_OK;
+}
+
 int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
   if (!t || !blob_host) return zf::einval("NULL argument");
   ZF_TRY_HIP(hipDeviceSynchronize());
@@ -894,6 +1044,7 @@ int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
 
 int zf_trainer_set_blob(zf_trainer_t* t, const float* blob_host) {
   if (!t || !blob_host) return zf::einval("NULL argument");
+  t->pend_mode = zf::kPendNone;
   ZF_TRY_HIP(hipDeviceSynchronize());
   ZF_TRY_HIP(hipMemcpy(t->d_nat, blob_host, t->nat_floats * sizeof(float), hipMemcpyHostToDevice));
   return ZF_OK;
@@ -974,6 +1125,7 @@ extern "C" {
 
 int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, const unsigned char* decay_mask) {
   if (!t || !chain) return zf::einval("NULL argument");
+  t->pend_mode = zf::kPendNone;
   const int S = chain->n_stages;
   if (S < 1) return zf::einval("optimiser chain: no stage");
   if (S > ZF_OPT_MAX_STAGES)

@@ -720,5 +720,27 @@ struct LatentConsts {
         tnm((float)std::log1p(-2.0 * 0.5 * std::erfc(5.0 / std::sqrt(2.0)))) {}
 };
 
+// bn_eval_fwd_kernel that also keeps Uhat = (u - mean) rstd, which the
+// BatchNorm scale gradient of an eval-mode reverse pass sums against gUbn
+// (zf_trainer_forward with train = 0).  Ubn and rstd_out are formed by the
+// same separately rounded operations, so they have bn_eval_fwd_kernel's bits.
+// Last in this header: the kernels above keep their places in the code object.
+__global__ void bn_eval_fwd_uhat_kernel(const float* __restrict__ s, const float* __restrict__ c,
+                                        const float* __restrict__ nat_bn, float* __restrict__ Uhat,
+                                        float* __restrict__ Ubn, float* __restrict__ rstd_out, int B, int D, int C,
+                                        int dt, int dc, int rot) {
+  const int DC = dc + C;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)B * DC) return;
+  const long long b = i / DC;
+  const int k = (int)(i - b * DC);
+  const float u = k < dc ? s[b * D + pmodi(dt + k + rot, D)] : c[b * C + (k - dc)];
+  const float rstd = 1.0f / sqrtf(nat_bn[DC + k] + kBnEps);
+  if (b == 0) rstd_out[k] = rstd;
+  const float uh = bn_hat(u, nat_bn[k], rstd);
+  Uhat[i] = uh;
+  Ubn[i] = bn_out(uh, nat_bn[2 * DC + k], nat_bn[3 * DC + k]);
+}
+
 }  // namespace
 }  // namespace zf

@@ -153,14 +153,15 @@ class Trainer:
     def _global(self, rows: int, global_rows: Optional[int]) -> int:
         return int(global_rows) if global_rows is not None else int(rows) * self.world
 
-    def _weights(self, w, rows: int) -> DeviceArray:
-        """This rank's ``rows`` weights on the device.  A host array is checked
-        (shape, finiteness); a DeviceArray is taken as it is, size apart."""
+    def _weights(self, w, rows: int, name: str = "w") -> DeviceArray:
+        """This rank's ``rows`` weights (or cotangents) on the device.  A host
+        array is checked (shape, finiteness); a DeviceArray is taken as it
+        is, size apart."""
         if isinstance(w, DeviceArray):
             if int(np.prod(w.shape)) != rows or w.dtype != np.float32:
-                raise ValueError(f"w must hold {rows} float32 weights, got {w.dtype} {w.shape}")
+                raise ValueError(f"{name} must hold {rows} float32 entries, got {w.dtype} {w.shape}")
             return w
-        return DeviceArray.from_numpy(check_weights(w, rows, "w"))
+        return DeviceArray.from_numpy(check_weights(w, rows, name))
 
     def loss_grad(self, x, c=None, update_stats: bool = False,
                   global_rows: Optional[int] = None, cond_grad: bool = False, w=None):
@@ -248,6 +249,95 @@ class Trainer:
             dx.ptr, None if dc is None else dc.ptr, N, L.stream()), "zf_trainer_log_prob_vjp")
         return lp, dx, dc
 
+    # ---- custom losses: the user's loss between a forward and a backward ----
+    def forward(self, x, c=None, *, train: bool = True, update_stats: Optional[bool] = None,
+                global_rows: Optional[int] = None):
+        """Per-row ``log_prob`` (rows,) float32 of ``flow.apply(..., train=train)``
+        at the trainer's parameters, with the activations kept for one
+        :meth:`backward` (zf_trainer_forward).  Any loss of these values is
+        then the caller's own code, as with the reference (train.py:64-86):
+
+            lp = tr.forward(x, c)
+            g = tr.backward(dloss_dlp(lp))
+            tr.apply_gradient(g)
+
+        ``train=True``: batch statistics, and the running statistics are
+        updated when ``update_stats`` (default: ``train``).  ``train=False``:
+        the stored statistics, nothing updated.  Host arrays in give a host
+        array out, a DeviceArray ``x`` a DeviceArray.  Data parallel: ``x`` is
+        this rank's shard of ``global_rows`` rows, as in :meth:`loss_grad`."""
+        train = bool(train)
+        update_stats = train if update_stats is None else bool(update_stats)
+        if update_stats and not train:
+            raise ValueError("update_stats=True needs train=True: eval mode reads the stored statistics")
+        xd, cd = self._dev(x, self.D), self._dev(c, self.C)
+        rows = xd.shape[0]
+        if rows > self.batch_max:
+            raise ValueError(f"forward takes at most batch_max = {self.batch_max} rows, got {rows}: "
+                             "micro-batch and accumulate the gradients")
+        lp = DeviceArray((rows,))
+        self._pending_rows = None
+        check(L.load_library().zf_trainer_forward(
+            self.handle, xd.ptr, _ptr(cd), rows, self._global(rows, global_rows), 1 if train else 0,
+            1 if update_stats else 0, lp.ptr, L.stream()), "zf_trainer_forward")
+        self._pending_rows = rows
+        self._pending_device = isinstance(x, DeviceArray)
+        return lp if isinstance(x, DeviceArray) else lp.numpy()
+
+    def backward(self, cotangent, *, cond_grad: bool = False):
+        """The gradient, in the natural blob layout, of
+        ``sum_b cotangent[b] * lp[b]`` over the global batch of the pending
+        :meth:`forward` — with ``cotangent = d loss / d lp`` the gradient of
+        the caller's loss (zf_trainer_backward; :meth:`grad_tree` turns it
+        into a FLAX tree).  ``cotangent`` (rows,): a host array, checked like
+        :func:`check_weights` before any device call, or a float32 DeviceArray.
+        ``cond_grad=True`` returns ``(g, gc)`` with ``gc`` (rows, C) the same
+        sum's gradient with respect to ``c``.  The results are DeviceArrays
+        when ``forward`` was given one.  Rows whose ``lp`` is not finite
+        contribute zeros.  One backward per forward: ``ValueError`` without a
+        pending one."""
+        rows = getattr(self, "_pending_rows", None)
+        if rows is None:
+            raise ValueError("backward needs a pending forward (one backward per forward; step, loss_grad, "
+                             "log_prob_vjp and apply_gradient drop it)")
+        cot = self._weights(cotangent, rows, "cotangent")
+        gc = self._gc_out(rows) if cond_grad else None
+        g = DeviceArray((self.program.blob.size,))
+        self._pending_rows = None
+        rc = L.load_library().zf_trainer_backward(self.handle, cot.ptr, g.ptr, _ptr(gc), L.stream())
+        if rc and "no forward pending" in L.load_library().zf_last_error().decode():
+            raise ValueError("backward needs a pending forward: another trainer call dropped it")
+        check(rc, "zf_trainer_backward")
+        self._last_grad = g
+        dev = self._pending_device
+        if cond_grad:
+            return (g, gc) if dev else (g.numpy(), gc.numpy())
+        return g if dev else g.numpy()
+
+    def apply_gradient(self, g=None) -> None:
+        """The optimiser update of :meth:`step` on a given gradient
+        (zf_trainer_apply_gradient): ``g`` a blob-layout host array or
+        DeviceArray, a FLAX ``params`` tree as :meth:`grad_tree` returns it
+        (edited, summed over micro-batches ...), or None for the gradient of
+        the last :meth:`backward`.  Data parallel: every rank passes the same
+        gradient, which is what ``backward`` returns."""
+        n = self.program.blob.size
+        if g is None:
+            gd = getattr(self, "_last_grad", None)
+            if gd is None:
+                raise ValueError("apply_gradient() without a gradient needs an earlier backward")
+        elif isinstance(g, DeviceArray):
+            gd = g
+        else:
+            if isinstance(g, dict):
+                g = tree_to_blob(self.program, g, np.float32)
+            gd = DeviceArray.from_numpy(np.ascontiguousarray(np.asarray(g, np.float32).reshape(-1)))
+        if int(np.prod(gd.shape)) != n or gd.dtype != np.float32:
+            raise ValueError(f"the gradient must hold {n} float32 entries (blob layout), got {gd.dtype} {gd.shape}")
+        self._pending_rows = None
+        check(L.load_library().zf_trainer_apply_gradient(self.handle, gd.ptr, L.stream()),
+              "zf_trainer_apply_gradient")
+
     def _step_rows(self, xptr: int, cptr: Optional[int], rows: int, global_rows: Optional[int] = None,
                    wptr: Optional[int] = None) -> None:
         """One step on ``rows`` device-resident rows (raw pointers; async);
@@ -333,7 +423,7 @@ def check_weights(w, rows: int, name: str) -> np.ndarray:
         raise ValueError(f"{name} must have shape ({rows},), got {a.shape}")
     a = np.ascontiguousarray(a, np.float32)
     if not np.isfinite(a).all():
-        raise ValueError(f"{name} holds {int((~np.isfinite(a)).sum())} non-finite weights")
+        raise ValueError(f"{name} holds {int((~np.isfinite(a)).sum())} non-finite values")
     return a
 
 
