@@ -487,6 +487,69 @@ int zf_trainer_forward(zf_trainer_t* trainer, const float* x, const float* c, in
 int zf_trainer_backward(zf_trainer_t* trainer, const float* cot, float* grad, float* gc, void* stream);
 int zf_trainer_apply_gradient(zf_trainer_t* trainer, const float* grad, void* stream);
 
+/* Gradients through sampling.  With the reference
+ * x = flow.apply(vars, c_or_n, method="sample") (flow.py:50-78) is an
+ * ordinary JAX function, and jax.grad of any loss of the samples works: the
+ * reverse-KL / variational fit E_z[log q(x(z)) - log p(x(z))] to a target
+ * density, amortised posteriors q(theta | c), importance-sampling proposals,
+ * samples fed to a differentiable simulator or a discriminator.  Two entries,
+ * with zf_trainer_apply_gradient as the optimiser half:
+ *
+ * zf_trainer_sample_forward: z (rows,D) latent rows and c (rows,C) or NULL on
+ *   the device (rows <= batch_max; rows / global_rows as zf_trainer_forward's
+ *   in eval mode, except that one device may pass global_rows > rows for a
+ *   micro-batch of a larger batch: rows are independent, global_rows only
+ *   picks the GEMM forms and the reduction leaves; nothing is exchanged).
+ *   x (rows,D) receives
+ *   bijector.inverse(z, c) as Flow.sample computes it (flow.py:76-77): eval
+ *   mode, BatchNorm on the stored mean / var (bijectors.py:367-371),
+ *   ShiftBounds.inverse on the stored xmin / xmax (:210-240), Roll.inverse.
+ *   log_q (rows,) or NULL receives
+ *     latent.log_prob(z) + sum over the ops of log_det_op,
+ *   log_det_op the op's FORWARD log-det (utils.py:121-139,
+ *   bijectors.py:186-207) at the inverse's own intermediate for that op:
+ *   what flow.apply(vars, x, c) gives for the sample before nan_to_num, up to
+ *   float32 rounding, wherever ShiftBounds' clamp is inactive.  A log_q that
+ *   is not finite is reported as such (-inf / +inf where the latent density
+ *   is, NaN from a NaN log-det), not as finfo.min.
+ *   A row whose spline inverse is not finite (the idx == K sliver of the
+ *   reference's fill-mode gather, utils.py:224-230) comes out as NaN in every
+ *   column of x, where the reference has NaN in the columns that depend on it.
+ *   ZF_EINVAL (nothing enqueued) while a ShiftBounds dim's stored bounds are
+ *   still the initial +-inf.  The pass stays pending for one
+ *   zf_trainer_sample_backward; the calls that drop a pending
+ *   zf_trainer_forward drop it too.  zf_trainer_backward does not take it
+ *   (ZF_EINVAL "no forward pending", nothing enqueued).
+ *
+ * zf_trainer_sample_backward: gx (rows,D) = d L / d x and glq (rows,) =
+ *   d L / d log_q of this rank's rows (glq NULL: zeros), on the device.  grad
+ *   (blob layout, fp32, device; NULL: the trainer's own buffer) receives
+ *     d / d blob of  sum over the GLOBAL batch of gx_b . x_b + glq_b log_q_b,
+ *   zero on the statistics entries and identical on every rank (only this
+ *   final gradient is exchanged); gz (rows,D) or NULL the same sum's gradient
+ *   with respect to z, gc (rows,C) or NULL with respect to c.
+ *     - The x path is the derivative of the reference's own inverse formula,
+ *       the quadratic root of utils.py:193-201 with the bin found on the yk
+ *       knots: no clamp, no epsilons.  (Not 1 / s'(x) of the forward spline,
+ *       whose den + 1e-5 and clamp make its derivative differ by ~1e-5.)
+ *     - The log_q path is the forward spline's reverse at x_t with the row's
+ *       glq as the log-det cotangent; its d / d x_t joins the cotangent on x_t
+ *       before the root formula is reversed.
+ *     - Latent columns outside [0, 1) are the identity: the cotangent passes
+ *       through and no parameter gradient arises.
+ *     - Rows whose x or log_q is not finite (the sliver above; a latent value
+ *       outside the latent's support) contribute exact zeros to grad and get
+ *       all-zero gz / gc rows: zf_trainer_backward's rule.  A deliberate
+ *       deviation: jax.grad would make the whole gradient NaN.
+ *   Needs a pending zf_trainer_sample_forward (ZF_EINVAL "no forward pending",
+ *   nothing enqueued: a pending zf_trainer_forward does not count); one
+ *   backward per forward.
+ * The trainer's limits apply (ZF_ENOTSUP at zf_trainer_create). */
+int zf_trainer_sample_forward(zf_trainer_t* trainer, const float* z, const float* c, int64_t rows,
+                              int64_t global_rows, float* x, float* log_q, void* stream);
+int zf_trainer_sample_backward(zf_trainer_t* trainer, const float* gx, const float* glq, float* grad, float* gz,
+                               float* gc, void* stream);
+
 /* Copy the trainer's natural blob (parameters + statistics) out / in. */
 int zf_trainer_get_blob(zf_trainer_t* trainer, float* blob_host);
 int zf_trainer_set_blob(zf_trainer_t* trainer, const float* blob_host);

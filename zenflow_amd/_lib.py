@@ -185,6 +185,8 @@ SIGNATURES = {
     "zf_trainer_forward": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     "zf_trainer_backward": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "zf_trainer_apply_gradient": (_int, [_vp, _vp, _vp]),
+    "zf_trainer_sample_forward": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "zf_trainer_sample_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zf_trainer_get_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_blob": (_int, [_vp, _vp]),
     "zf_trainer_set_optim_chain": (_int, [_vp, _vp, _vp]),

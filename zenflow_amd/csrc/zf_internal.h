@@ -63,4 +63,21 @@ int dense_gemm(long long Mg, int M, int N, int K, const float* A, int lda, const
 int spline_rows(bool inverse, const float* s_in, float* s_out, const float* P, float* ld, int B, int D, int dt,
                 int K, int rot, hipStream_t st);
 
+// Gradients through sampling: the launchers of zf_sample_grad.hip
+// (zf_train_sample.h documents the kernels), called by zf_train.hip's
+// trainer_sample_forward / trainer_sample_reverse.
+int spline_inv_ld_launch(const float* s_in, float* s_out, const float* P, float* ld, float* dead, int B, int D, int dt,
+                         int K, int rot, hipStream_t st);
+int spline_inv_bwd_launch(const float* s_y, const float* s_x, const float* P, const float* g_out, const float* glr,
+                          const float* mask, float* g_in, float* gP, int B, int D, int dt, int K, int rot,
+                          hipStream_t st);
+int sb_eval_inv_launch(const float* s1, float* s0, float* x, const float* sb, float* ld, const float* lat,
+                       const float* fin, float* mask, float* log_q, int B, int D, hipStream_t st);
+int sb_eval_inv_bwd_launch(const float* s1, const float* gx, const float* ce, const float* mask, const float* sb,
+                           float* g, int B, int D, hipStream_t st);
+int sample_rot_in_launch(const float* z, float* s, int B, int D, int rot, hipStream_t st);
+int sample_mask_cot_launch(const float* glq, const float* mask, float* ce, int B, hipStream_t st);
+int sample_gz_out_launch(const float* g, const float* gl, const float* mask, float* gz, int B, int D, int rot,
+                         hipStream_t st);
+
 }  // namespace zf

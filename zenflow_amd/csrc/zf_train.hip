@@ -20,7 +20,10 @@
 // its kernels are in the headers below, one concern each, all part of this
 // one translation unit: zf_gemm.h (GEMMs and the gemm() dispatcher),
 // zf_reduce.h (batch reductions, weight gradients), zf_train_kernels.h
-// (element-wise kernels) and zf_train_spline.h (RQ-spline rows).
+// (element-wise kernels) and zf_train_spline.h (RQ-spline rows).  The
+// gradients through sampling (zf_trainer_sample_forward / _sample_backward:
+// flow.py:50-78 as a differentiable function) are host code here over the
+// same helpers; their kernels are zf_train_sample.h in zf_sample_grad.hip.
 #include "zf_gemm.h"
 #include "zf_internal.h"
 #include "zf_optim.h"
@@ -108,13 +111,19 @@ struct zf_trainer {
   // zf_trainer_forward's pass, waiting for its zf_trainer_backward (kPend*)
   int pend_mode = 0;
   int64_t pend_rows = 0, pend_global = 0;
+  // gradients through sampling (zf_trainer_sample_forward / _backward)
+  float* d_sm = nullptr;      // [bmax] the pass's row mask: 1 where x and log_q are finite
+  float* d_lq = nullptr;      // [bmax] the latent's log-density of the pass's rows
+  float* d_gl = nullptr;      // [bmax][D] d log_q's share of d / d z at the latent
+  bool sb_ok = false;         // the stored ShiftBounds bounds were seen finite (they only widen)
 };
 
 namespace zf {
 namespace {
 
 // zf_trainer::pend_mode: no forward pending, or the mode zf_trainer_forward ran in
-enum { kPendNone = 0, kPendTrain = 1, kPendEval = 2 };
+// (kPendSample: zf_trainer_sample_forward's inverse pass, which only zf_trainer_sample_backward takes)
+enum { kPendNone = 0, kPendTrain = 1, kPendEval = 2, kPendSample = 3 };
 
 float* dmalloc(zf_trainer* t, int64_t n, int& rc) {
   if (rc) return nullptr;
@@ -247,6 +256,9 @@ int zf_trainer_create(const zf_flow_desc* desc_in, const float* blob_host, int64
     nb.rstd = zf::dmalloc(t, DC, rc);
   }
   t->d_w = zf::dmalloc(t, B, rc);  // last: the buffers above keep the places they had without it
+  t->d_sm = zf::dmalloc(t, B, rc);  // the sampling pass's, after it for the same reason
+  t->d_lq = zf::dmalloc(t, B, rc);
+  t->d_gl = zf::dmalloc(t, B * D, rc);
   hipError_t e = hipSuccess;
   if (!rc) e = hipMemcpy(t->d_nat, blob_host, need * sizeof(float), hipMemcpyHostToDevice);
   if (!rc && e == hipSuccess) e = hipMemcpy(t->d_mask, param_mask, need, hipMemcpyHostToDevice);
@@ -897,6 +909,166 @@ int run_step(zf_trainer_t* t, const BatchArgs& a) {
   return copy_loss(t, a);
 }
 
+// ---- gradients through sampling -------------------------------------------------
+// x = bijector.inverse(z, c) as a differentiable op (flow.py:76-77): eval mode
+// only, BatchNorm on the stored statistics (bijectors.py:367-371), ShiftBounds
+// on the stored bounds (:210-240).  The latent rows are staged in the last
+// state and the chain is walked from the last op to the first; for a coupling
+// the conditioning columns are the same on both sides, so the conditioner runs
+// on the op's input state of this pass (bn_eval_fwd_uhat_kernel +
+// nsc_dense_fwd, the eval forward's own launches) and the spline inverse
+// follows.  The states end up where a forward pass on x would leave them, the
+// activations in t->nsc[i]; d_ld collects every op's forward log-det at the
+// inverse's own intermediate, d_sm the row mask.
+int trainer_sample_forward(zf_trainer_t* t, int B, long long Bg, float* x_out, float* lq_out, hipStream_t st) {
+  const int D = t->D, C = t->C;
+  const zf_flow_desc& desc = t->desc;
+  float* nat = t->d_nat;
+  const std::vector<float*>& sp = t->sp;
+  const std::vector<int>& rots = t->rots;
+  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
+  ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
+  ZF_TRY_HIP(hipMemsetAsync(t->d_sm, 0, (size_t)B * sizeof(float), st));
+  // the latent's log-density (on the zero log-det) and its finite flag; the gz
+  // output is rewritten by the reverse pass
+  const LatentConsts lc(desc);
+  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld,
+                     (const float*)nullptr, B, D, rots[desc.n_ops], lc.lt, lc.a, lc.betac, lc.tnm, t->d_lq, t->d_ce,
+                     t->d_g0);
+  ZF_CHECK_LAUNCH("latent_vjp_kernel");
+  int rc;
+  for (int i = desc.n_ops - 1; i >= 0; --i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind == ZF_OP_ROLL || op.kind == ZF_OP_SHIFT_BOUNDS) continue;  // Roll: index map; ShiftBounds (first op): below
+    if (op.kind != ZF_OP_NSC) return einval("op %d: unknown kind", i);
+    int dt, dc, DC, S;
+    nsc_dims(t, op, dt, dc, DC, S);
+    zf_trainer::NscBufs& nb = t->nsc[i];
+    const int rot = rots[i];
+    hipLaunchKernelGGL(bn_eval_fwd_uhat_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st,
+                       (const float*)sp[i + 1], (const float*)t->d_c, (const float*)(nat + op.off_bn), nb.Uhat, nb.Ubn,
+                       nb.rstd, B, D, C, dt, dc, rot);
+    ZF_CHECK_LAUNCH("bn_eval_fwd_uhat_kernel");
+    if ((rc = nsc_dense_fwd(t, op, nb, Bg, B, DC, dt * S, st))) return rc;
+    if ((rc = spline_inv_ld_launch(sp[i + 1], sp[i], nb.P, t->d_ld, t->d_sm, B, D, dt, op.knots, rot, st))) return rc;
+  }
+  return sb_eval_inv_launch(sp[sb_first ? 1 : 0], sp[0], x_out, sb_first ? nat + desc.ops[0].off_sb : nullptr, t->d_ld,
+                            t->d_lq, t->d_ce, t->d_sm, lq_out, B, D, st);
+}
+
+// Its reverse: from gx = d L / d x (and glq = d L / d log_q, NULL: zeros) of
+// this rank's rows to the fp32 gradient G, gz and gc.  Ops from first to
+// last: the spline inverse's reverse, then the ra.eval sequence of
+// trainer_reverse on the same helpers (input-gradient GEMMs, deferred
+// weight-gradient GEMMs, the BatchNorm scale / bias gradients from the leaf
+// tree, bn_eval_bwd_kernel with the pass's row mask in place of ce), the same
+// cast and rank exchange.  G64 needs no clearing, as there.
+int trainer_sample_reverse(zf_trainer_t* t, int B, long long Bg, const float* gx, const float* glq, float* G,
+                           float* gz, float* gc_out, hipStream_t st) {
+  const int D = t->D, C = t->C, W = t->comm.world;
+  float* const gc = C > 0 ? gc_out : nullptr;
+  const zf_flow_desc& desc = t->desc;
+  float* nat = t->d_nat;
+  double* G64 = t->d_g64;
+  const std::vector<float*>& sp = t->sp;
+  const std::vector<int>& rots = t->rots;
+  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
+  const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
+  int rc;
+  // d L / d log_q per row: where log_q is finite (latent_vjp_kernel's rule, on
+  // the whole chain's log-det) and the row counts; its share of gz
+  if (glq) {
+    const LatentConsts lc(desc);
+    hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, glq, B, D,
+                       rots[desc.n_ops], lc.lt, lc.a, lc.betac, lc.tnm, (float*)nullptr, t->d_ce, t->d_gl);
+    ZF_CHECK_LAUNCH("latent_vjp_kernel");
+  }
+  if ((rc = sample_mask_cot_launch(glq ? t->d_ce : nullptr, t->d_sm, t->d_ce, B, st))) return rc;
+  float* g = t->d_g0;
+  float* g_next = t->d_g1;
+  rc = sb_eval_inv_bwd_launch(sp[sb_first ? 1 : 0], gx, t->d_ce, t->d_sm,
+                              sb_first ? nat + desc.ops[0].off_sb : nullptr, g, B, D, st);
+  if (rc) return rc;
+  zf::WgradQueue wq;
+  wq.tb.count = 0;
+  wq.gq.count = 0;
+  int gc_assign = 1;  // the first coupling met assigns gc
+  for (int i = 0; i < desc.n_ops; ++i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind != ZF_OP_NSC) continue;  // Roll: index map; ShiftBounds (first op): above
+    int dt, dc, DC, S;
+    nsc_dims(t, op, dt, dc, DC, S);
+    zf_trainer::NscBufs& nb = t->nsc[i];
+    const int r = rots[i];
+    // spline: g (d / d state i) -> g_next (d / d state i + 1, transformed columns), gP
+    rc = spline_inv_bwd_launch(sp[i + 1], sp[i], nb.P, g, t->d_ce, t->d_sm, g_next, nb.gP, B, D, dt, op.knots, r, st);
+    if (rc) return rc;
+    DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
+    for (int l = op.n_hidden; l >= 0; --l) {
+      const int in_w = dg.in_w(l);
+      const float* hin = l == 0 ? nb.Ubn : nb.H[l - 1];
+      const int cap = pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * dg.out_w))));
+      rc = wgrad_deferred(wq, in_w, dg.out_w, B, leaves_for(B, Bg, W, cap), hin, dg.gout, G64 + op.off_w[l],
+                          G64 + op.off_b[l], t->d_ws, t->d_ws2, st);
+      if (rc) return rc;
+      if ((rc = wgrad_before_write(wq, dg.gin(l), st))) return rc;
+      if ((rc = dg.layer(l, Bg, B, st))) return rc;
+    }
+    float* bn = nat + op.off_bn;
+    double* gbn = G64 + op.off_bn;
+    hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, nb.gU, nb.Uhat, B,
+                       DC, lbn.rows, lbn.n, t->d_leaf);
+    ZF_CHECK_LAUNCH("leaf_colsums_kernel");
+    if ((rc = launch_tree_cols(t->d_leaf, lbn.n, 2 * DC, t->d_roots, st, t->d_leaf2))) return rc;
+    ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, t->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+    ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, t->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
+                       (const float*)(bn + 2 * DC), (const float*)nb.rstd, (const float*)t->d_sm, g_next, gc, gc_assign,
+                       B, D, C, dt, dc, r);
+    ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
+    gc_assign = 0;
+    std::swap(g, g_next);
+  }
+  if ((rc = wgrad_flush(wq, st))) return rc;
+  if (gc && gc_assign)  // no coupling: x does not depend on c
+    ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * C * sizeof(float), st));
+  if (gz && (rc = sample_gz_out_launch(g, glq ? t->d_gl : nullptr, t->d_sm, gz, B, D, rots[desc.n_ops], st))) return rc;
+  // ---- the gradient: (all ranks' fp64 shares, tree over ranks) -> fp32, as trainer_reverse ----
+  if (W > 1) {
+    rc = t->comm.allgather(t->comm.ctx, G64, t->d_gath, (size_t)t->nat_floats * sizeof(double), st);
+    if (rc) return rc;
+#define ZF_L(NM) hipLaunchKernelGGL((tree_cols_cast_kernel<NM>), dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, \
+                                    (const double*)t->d_gath, W, (long long)t->nat_floats, G)
+    ZF_NMAX_DISPATCH(W, ZF_L);
+#undef ZF_L
+    ZF_CHECK_LAUNCH("tree_cols_cast_kernel");
+  } else {
+    hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, G64,
+                       (long long)t->nat_floats, G, (float*)nullptr, t->opt.b1, t->opt.b2);
+    ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
+  }
+  return ZF_OK;
+}
+
+// ZF_EINVAL while a ShiftBounds dim that maps through the stored xmin / xmax
+// still holds the initial +-inf (no train-mode pass has run): its inverse is
+// undefined.  Read back once; training only widens finite bounds.
+int check_sample_bounds(zf_trainer_t* t, hipStream_t st) {
+  const zf_flow_desc& desc = t->desc;
+  if (t->sb_ok || desc.n_ops == 0 || desc.ops[0].kind != ZF_OP_SHIFT_BOUNDS) return ZF_OK;
+  std::vector<float> rows((size_t)8 * t->D);
+  ZF_TRY_HIP(hipStreamSynchronize(st));
+  ZF_TRY_HIP(hipMemcpy(rows.data(), t->d_nat + desc.ops[0].off_sb, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int j = 0; j < t->D; ++j) {
+    if ((int)rows[8 * j] == ZF_SB_BOTH) continue;
+    if (!std::isfinite(rows[8 * j + 3]) || !std::isfinite(rows[8 * j + 4]))
+      return einval("ShiftBounds: the stored bounds of dim %d are still the initial +-inf (no train-mode pass has set "
+                    "them): the inverse is undefined", j);
+  }
+  t->sb_ok = true;
+  return ZF_OK;
+}
+
 }  // namespace
 }  // namespace zf
 
@@ -1010,7 +1182,8 @@ int zf_trainer_forward(zf_trainer_t* t, const float* x, const float* c, int64_t 
 
 int zf_trainer_backward(zf_trainer_t* t, const float* cot, float* grad, float* gc, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  if (t->pend_mode == zf::kPendNone) return zf::einval("no forward pending");
+  if (t->pend_mode != zf::kPendTrain && t->pend_mode != zf::kPendEval)  // a sampling pass is not a forward
+    return zf::einval("no forward pending");
   const bool eval = t->pend_mode == zf::kPendEval;
   t->pend_mode = zf::kPendNone;  // one backward per forward
   hipStream_t st = (hipStream_t)stream;
@@ -1035,6 +1208,46 @@ int zf_trainer_apply_gradient(zf_trainer_t* t, const float* grad, void* stream) 
   return ZF_OK;
 }
 
+// ---- gradients through sampling: sample_forward, sample_backward ----
+int zf_trainer_sample_forward(zf_trainer_t* t, const float* z, const float* c, int64_t rows, int64_t global_rows,
+                              float* x, float* log_q, void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  t->pend_mode = zf::kPendNone;
+  hipStream_t st = (hipStream_t)stream;
+  // check_batch's rules, but for global_rows on one device: the pass has no
+  // batch statistics, so there a larger global_rows only declares the rows a
+  // micro-batch of that batch (it picks the GEMM forms and the leaf layout)
+  if (rows < 1 || rows > t->bmax)
+    return zf::einval("batch %lld outside [1, %lld]", (long long)rows, (long long)t->bmax);
+  if (!z) return zf::einval("z is NULL");
+  if (t->C > 0 && !c) return zf::einval("flow is conditional but c is NULL");
+  if (global_rows < rows)
+    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
+  if (!x) return zf::einval("x is NULL");
+  if (t->desc.latent == ZF_LATENT_NONE) return zf::einval("flow has no latent distribution");
+  int rc = zf::check_sample_bounds(t, st);
+  if (rc) return rc;
+  const int B = (int)rows;
+  if (t->C > 0)
+    ZF_TRY_HIP(hipMemcpyAsync(t->d_c, c, (size_t)rows * t->C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if ((rc = zf::sample_rot_in_launch(z, t->sp[t->n_ops], B, t->D, t->rots[t->n_ops], st))) return rc;
+  if ((rc = zf::trainer_sample_forward(t, B, global_rows, x, log_q, st))) return rc;
+  t->pend_mode = zf::kPendSample;
+  t->pend_rows = rows;
+  t->pend_global = global_rows;
+  return ZF_OK;
+}
+
+int zf_trainer_sample_backward(zf_trainer_t* t, const float* gx, const float* glq, float* grad, float* gz, float* gc,
+                               void* stream) {
+  if (!t) return zf::einval("trainer is NULL");
+  if (t->pend_mode != zf::kPendSample) return zf::einval("no forward pending");
+  if (!gx) return zf::einval("gx is NULL");
+  t->pend_mode = zf::kPendNone;  // one backward per forward
+  return zf::trainer_sample_reverse(t, (int)t->pend_rows, t->pend_global, gx, glq, grad ? grad : t->d_grad, gz, gc,
+                                    (hipStream_t)stream);
+}
+
 int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
   if (!t || !blob_host) return zf::einval("NULL argument");
   ZF_TRY_HIP(hipDeviceSynchronize());
@@ -1045,6 +1258,7 @@ int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
 int zf_trainer_set_blob(zf_trainer_t* t, const float* blob_host) {
   if (!t || !blob_host) return zf::einval("NULL argument");
   t->pend_mode = zf::kPendNone;
+  t->sb_ok = false;
   ZF_TRY_HIP(hipDeviceSynchronize());
   ZF_TRY_HIP(hipMemcpy(t->d_nat, blob_host, t->nat_floats * sizeof(float), hipMemcpyHostToDevice));
   return ZF_OK;

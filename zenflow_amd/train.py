@@ -338,6 +338,120 @@ class Trainer:
         check(L.load_library().zf_trainer_apply_gradient(self.handle, gd.ptr, L.stream()),
               "zf_trainer_apply_gradient")
 
+    # ---- gradients through sampling: a loss of the samples, not of log_prob ----
+    def sample_forward(self, conditions_or_size, *, seed: int = 0, z=None, global_rows: Optional[int] = None):
+        """``(x, log_q)``: the samples ``x = bijector.inverse(z, c)`` (rows, D)
+        of ``Flow.sample`` (flow.py:50-78; eval mode, stored statistics) at the
+        trainer's parameters and their log-density ``log_q`` (rows,) under the
+        flow — the latent's log_prob of ``z`` plus every op's forward log-det
+        at the inverse's own intermediates — with the activations kept for
+        one :meth:`sample_backward` (zf_trainer_sample_forward).  A reverse-KL
+        fit to a target density ``log_p`` is three calls:
+
+            x, log_q = tr.sample_forward(n, seed=step)
+            g = tr.sample_backward(-dlogp_dx(x) / n, np.full(n, 1 / n, np.float32))
+            tr.apply_gradient(g)
+
+        ``conditions_or_size``: the conditions ``c`` (rows, C) or, for an
+        unconditional flow, the number of rows.  ``z=None`` draws
+        ``flow.latent.sample(rows, PRNGKey(seed))`` on the device, the bits
+        ``Flow.sample(..., seed=seed)`` starts from; else ``z`` (rows, D) is a
+        host array or a DeviceArray.  Host arrays in give host arrays out, a
+        DeviceArray ``c`` or ``z`` DeviceArrays.  ``log_q`` is not finite
+        where the latent's density of ``z`` is not; such rows count for
+        nothing in :meth:`sample_backward`.  Data parallel: the rows are this
+        rank's shard of ``global_rows`` rows, as in :meth:`forward`."""
+        if isinstance(conditions_or_size, (int, np.integer)):
+            rows, c = int(conditions_or_size), None
+        else:
+            c = conditions_or_size
+            rows = int(c.shape[0])
+        if self.C and c is None:
+            raise ValueError(f"this flow is conditional: pass the conditions (rows, {self.C}), not a size")
+        if not self.C and c is not None:
+            raise ValueError("this flow is unconditional: pass the number of rows")
+        if rows < 1 or rows > self.batch_max:
+            raise ValueError(f"sample_forward takes 1 to batch_max = {self.batch_max} rows, got {rows}: "
+                             "micro-batch and accumulate the gradients")
+        cd = self._dev(c, self.C)
+        if cd is not None and tuple(cd.shape) != (rows, self.C):
+            raise ValueError(f"conditions must have shape ({rows}, {self.C}), got {tuple(cd.shape)}")
+        if z is None:
+            zd = self._latent_draw(rows, seed)
+        else:
+            zd = self._dev(z, self.D)
+            if tuple(zd.shape) != (rows, self.D) or zd.dtype != np.float32:
+                raise ValueError(f"z must hold ({rows}, {self.D}) float32 entries, got {zd.dtype} {tuple(zd.shape)}")
+        x, lq = DeviceArray((rows, self.D)), DeviceArray((rows,))
+        self._pending_rows = None
+        self._pending_sample = None
+        check(L.load_library().zf_trainer_sample_forward(
+            self.handle, zd.ptr, _ptr(cd), rows, self._global(rows, global_rows), x.ptr, lq.ptr, L.stream()),
+            "zf_trainer_sample_forward")
+        self._pending_sample = rows
+        self._pending_device = isinstance(c, DeviceArray) or isinstance(z, DeviceArray)
+        return (x, lq) if self._pending_device else (x.numpy(), lq.numpy())
+
+    def _latent_draw(self, rows: int, seed: int) -> DeviceArray:
+        """``flow.latent.sample(rows, PRNGKey(seed))``, left on the device."""
+        from .engine import _latent_code
+        from .random import key_to_seed
+
+        if self.flow is None:
+            raise ValueError("sample_forward(z=None) needs the trainer's flow for its latent: pass z")
+        code, param = _latent_code(self.flow.latent)
+        z = DeviceArray((rows, self.D))
+        check(L.load_library().zf_latent_sample(code, param, key_to_seed(PRNGKey(seed)), z.ptr, rows, self.D,
+                                                L.stream()), "zf_latent_sample")
+        return z
+
+    def sample_backward(self, gx, glog_q=None, *, cond_grad: bool = False, latent_grad: bool = False):
+        """The gradient, in the natural blob layout, of
+        ``sum_b gx[b] . x[b] + glog_q[b] * log_q[b]`` over the global batch of
+        the pending :meth:`sample_forward` — with ``gx = d loss / d x`` and
+        ``glog_q = d loss / d log_q`` the gradient of the caller's loss of the
+        samples (zf_trainer_sample_backward; :meth:`grad_tree` and
+        :meth:`apply_gradient` take it unchanged).  ``gx`` (rows, D) and
+        ``glog_q`` (rows,), None for zeros: host arrays, checked for shape and
+        finiteness before any device call, or float32 DeviceArrays.
+        ``cond_grad=True`` / ``latent_grad=True`` also return the same sum's
+        gradient with respect to ``c`` (rows, C) / ``z`` (rows, D), in that
+        order after ``g``.  The results are DeviceArrays when
+        ``sample_forward`` was given one.  Rows whose ``x`` or ``log_q`` is
+        not finite contribute zeros and get zero ``gc`` / ``gz`` rows.  One
+        backward per forward: ``ValueError`` without a pending one."""
+        rows = getattr(self, "_pending_sample", None)
+        if rows is None:
+            raise ValueError("sample_backward needs a pending sample_forward (one backward per forward; forward, "
+                             "step, loss_grad, log_prob_vjp and apply_gradient drop it)")
+        if isinstance(gx, DeviceArray):
+            if int(np.prod(gx.shape)) != rows * self.D or gx.dtype != np.float32:
+                raise ValueError(f"gx must hold ({rows}, {self.D}) float32 entries, got {gx.dtype} {gx.shape}")
+            gxd = gx
+        else:
+            a = np.asarray(gx)
+            if a.shape != (rows, self.D):
+                raise ValueError(f"gx must have shape ({rows}, {self.D}), got {a.shape}")
+            a = np.ascontiguousarray(a, np.float32)
+            if not np.isfinite(a).all():
+                raise ValueError(f"gx holds {int((~np.isfinite(a)).sum())} non-finite values")
+            gxd = DeviceArray.from_numpy(a)
+        gl = None if glog_q is None else self._weights(glog_q, rows, "glog_q")
+        gc = self._gc_out(rows) if cond_grad else None
+        gz = DeviceArray((rows, self.D)) if latent_grad else None
+        g = DeviceArray((self.program.blob.size,))
+        self._pending_sample = None
+        rc = L.load_library().zf_trainer_sample_backward(self.handle, gxd.ptr, _ptr(gl), g.ptr, _ptr(gz), _ptr(gc),
+                                                         L.stream())
+        if rc and "no forward pending" in L.load_library().zf_last_error().decode():
+            raise ValueError("sample_backward needs a pending sample_forward: another trainer call dropped it")
+        check(rc, "zf_trainer_sample_backward")
+        self._last_grad = g
+        out = [g] + ([gc] if cond_grad else []) + ([gz] if latent_grad else [])
+        if not self._pending_device:
+            out = [o.numpy() for o in out]
+        return out[0] if len(out) == 1 else tuple(out)
+
     def _step_rows(self, xptr: int, cptr: Optional[int], rows: int, global_rows: Optional[int] = None,
                    wptr: Optional[int] = None) -> None:
         """One step on ``rows`` device-resident rows (raw pointers; async);
