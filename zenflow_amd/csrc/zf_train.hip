@@ -20,10 +20,20 @@
 // its kernels are in the headers below, one concern each, all part of this
 // one translation unit: zf_gemm.h (GEMMs and the gemm() dispatcher),
 // zf_reduce.h (batch reductions, weight gradients), zf_train_kernels.h
-// (element-wise kernels) and zf_train_spline.h (RQ-spline rows).  The
-// gradients through sampling (zf_trainer_sample_forward / _sample_backward:
-// flow.py:50-78 as a differentiable function) are host code here over the
-// same helpers; their kernels are zf_train_sample.h in zf_sample_grad.hip.
+// (element-wise kernels) and zf_train_spline.h (RQ-spline rows).  The host
+// logic is a handful of passes over the coupling chain, each a loop of the
+// per-coupling helpers they share (nsc_dense_fwd, nsc_eval_conditioner,
+// spline_reverse, nsc_reverse_mlp, bn_param_grads, bn_eval_reverse,
+// latent_vjp_launch, close_gradient):
+//   forward   trainer_forward_train, trainer_forward_eval, and
+//             trainer_sample_forward (flow.py:50-78 as a differentiable
+//             function; its kernels are zf_train_sample.h in zf_sample_grad.hip)
+//   reverse   trainer_reverse (train and eval mode), trainer_sample_reverse
+//   whole     trainer_body (train-mode forward + loss + trainer_reverse),
+//             trainer_vjp_chunk (eval forward + the input gradients)
+// behind the entries run_loss_grad / run_step (the eight loss_grad / step
+// entries), zf_trainer_log_prob_vjp, zf_trainer_forward / _backward /
+// _apply_gradient and zf_trainer_sample_forward / _sample_backward.
 #include "zf_gemm.h"
 #include "zf_internal.h"
 #include "zf_optim.h"
@@ -46,6 +56,7 @@ struct zf_trainer {
   int64_t bmax = 0;
   zf_optim_desc opt;
   long long t = 0;  // optimiser step count (host mirror of d_step)
+  bool sb_first = false;  // the chain starts with a ShiftBounds (the only place it may stand)
   std::vector<float> sb_modes, sb_prm;  // ShiftBounds pre-transform per dim (colstats)
   float* d_nat = nullptr;
   float* d_grad = nullptr;
@@ -125,6 +136,11 @@ namespace {
 // (kPendSample: zf_trainer_sample_forward's inverse pass, which only zf_trainer_sample_backward takes)
 enum { kPendNone = 0, kPendTrain = 1, kPendEval = 2, kPendSample = 3 };
 
+// Every entry that overwrites the arena drops the pending pass (kPendNone); a forward that ran records its batch.
+inline void set_pending(zf_trainer* t, int mode, int64_t rows = 0, int64_t global_rows = 0) {
+  t->pend_mode = mode, t->pend_rows = rows, t->pend_global = global_rows;
+}
+
 float* dmalloc(zf_trainer* t, int64_t n, int& rc) {
   if (rc) return nullptr;
   void* p = nullptr;
@@ -183,7 +199,8 @@ int zf_trainer_create(const zf_flow_desc* desc_in, const float* blob_host, int64
   t->bmax = batch_max;
   t->opt = *opt;
   const int64_t B = batch_max, D = desc.dim;
-  if (desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS) {
+  t->sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
+  if (t->sb_first) {
     const float* row = blob_host + desc.ops[0].off_sb;
     for (int j = 0; j < D; ++j) {
       const int mode = (int)row[8 * j];
@@ -337,14 +354,26 @@ struct BatchArgs {
   hipStream_t stream;
 };
 
+// What check_batch holds a batch to.
+enum BatchRule {
+  kBatchShard,    // this rank's shard of global_rows rows; on one device global_rows == rows
+  kBatchSample,   // latent rows z of a sampling pass: it has no batch statistics, so on one device a larger
+                  // global_rows only declares the rows a micro-batch of that batch (it picks the GEMM forms
+                  // and the leaf layout)
+  kBatchChunked,  // N rows of zf_trainer_log_prob_vjp, taken bmax at a time: no upper bound
+};
+
 // Everything that can be wrong with a batch, before anything is enqueued.
-int check_batch(const zf_trainer_t* t, const BatchArgs& a) {
+int check_batch(const zf_trainer_t* t, const BatchArgs& a, BatchRule rule = kBatchShard) {
   if (!t) return einval("trainer is NULL");
-  if (a.rows < 1 || a.rows > t->bmax)
+  if (rule == kBatchChunked) {
+    if (a.rows < 1) return einval("N must be at least 1");
+  } else if (a.rows < 1 || a.rows > t->bmax) {
     return einval("batch %lld outside [1, %lld]", (long long)a.rows, (long long)t->bmax);
-  if (!a.x) return einval("x is NULL");
+  }
+  if (!a.x) return einval("%s is NULL", rule == kBatchSample ? "z" : "x");
   if (t->C > 0 && !a.c) return einval("flow is conditional but c is NULL");
-  if (a.global_rows < a.rows || (t->comm.world == 1 && a.global_rows != a.rows))
+  if (a.global_rows < a.rows || (rule == kBatchShard && t->comm.world == 1 && a.global_rows != a.rows))
     return einval("global_rows %lld vs rows %lld (world %d)", (long long)a.global_rows, (long long)a.rows,
                   t->comm.world);
   return ZF_OK;
@@ -375,11 +404,14 @@ int dp_combine(zf_trainer_t* t, double* roots, long long n, hipStream_t st) {
   return launch_tree_cols((const double*)t->d_gath, W, n, roots, st);
 }
 
-// ---- The coupling chain shared by the train-mode step (trainer_body) and the
-// eval-mode input gradients (trainer_vjp_chunk) ----
+// ---- The per-coupling helpers the passes share.  i is the coupling's place in
+// the chain: its op is t->desc.ops[i], its activations t->nsc[i], its column
+// rotation t->rots[i].  B: this rank's rows; Bg: the batch that picks the GEMM
+// forms and the leaf layouts (the global batch; the chunk itself in
+// trainer_vjp_chunk) ----
 
 // The Dense chain of one coupling's conditioner: nb.Ubn -> Z[l], H[l] = act(Z[l]) -> nb.P
-// (dt * S raw spline parameters per row).  Bg: the batch that picks the GEMM form.
+// (dt * S raw spline parameters per row).
 int nsc_dense_fwd(zf_trainer_t* t, const zf_op_desc& op, zf_trainer::NscBufs& nb, long long Bg, int B, int DC,
                   int out_last, hipStream_t st) {
   const float* nat = t->d_nat;
@@ -400,36 +432,154 @@ int nsc_dense_fwd(zf_trainer_t* t, const zf_op_desc& op, zf_trainer::NscBufs& nb
   return ZF_OK;
 }
 
-// The input gradients of one coupling's Dense chain, last layer first.  gout
-// (out_w wide) is d loss / d (layer l's output); layer l's GEMM writes
-// d loss / d (its input) to gin(l): nb.gU for layer 0, else nb.gA / nb.gB in turn.
-struct DgradChain {
-  zf_trainer_t* t;
-  const zf_op_desc& op;
-  zf_trainer::NscBufs& nb;
-  int DC;
-  const float* gout;
-  int out_w;
-  int which = 0;
-  int in_w(int l) const { return l == 0 ? DC : op.hidden[l - 1]; }
-  float* gin(int l) const { return l == 0 ? nb.gU : (which ? nb.gB : nb.gA); }
-  // g_in = gout . W_l^T (through the activation of layer l-1 when l > 0), then on to layer l-1
-  int layer(int l, long long Bg, int B, hipStream_t st) {
-    float* const g = gin(l);
-    const int w = in_w(l);
-    const int rc = gemm(true, Bg, B, w, out_w, gout, out_w, t->d_nat + op.off_w[l], out_w, g, w, st,
-                        l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? nb.Z[l - 1] : nullptr, op.act,
-                        t->splitq ? t->d_split : nullptr, kSplitFloats);
-    if (rc) return rc;
-    if (l > 0) {
-      gout = g;
-      out_w = w;
-      which ^= 1;
-    }
-    return ZF_OK;
+// One coupling's conditioner in eval mode, from the state that holds its
+// conditioning columns: BatchNorm on the stored mean / var (nb.Ubn, nb.rstd;
+// keep_uhat: also nb.Uhat, which the BatchNorm scale gradient reads, Ubn has
+// the same bits either way), then the Dense chain to nb.P.
+int nsc_eval_conditioner(zf_trainer_t* t, int i, const float* state_in, bool keep_uhat, int B, long long Bg,
+                         hipStream_t st) {
+  const zf_op_desc& op = t->desc.ops[i];
+  zf_trainer::NscBufs& nb = t->nsc[i];
+  int dt, dc, DC, S;
+  nsc_dims(t, op, dt, dc, DC, S);
+  const float* bn = t->d_nat + op.off_bn;
+  if (keep_uhat) {
+    hipLaunchKernelGGL(bn_eval_fwd_uhat_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, state_in,
+                       (const float*)t->d_c, bn, nb.Uhat, nb.Ubn, nb.rstd, B, t->D, t->C, dt, dc, t->rots[i]);
+    ZF_CHECK_LAUNCH("bn_eval_fwd_uhat_kernel");
+  } else {
+    hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, state_in,
+                       (const float*)t->d_c, bn, nb.Ubn, nb.rstd, B, t->D, t->C, dt, dc, t->rots[i]);
+    ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
   }
-};
+  return nsc_dense_fwd(t, op, nb, Bg, B, DC, dt * S, st);
+}
 
+// The reverse of one coupling's spline: g = d / d (state i + 1) -> g_prev
+// (the transformed columns of d / d (state i)) and nb.gP.  ce: d / d log_det
+// per row (NULL: gl for every row).
+int spline_reverse(zf_trainer_t* t, int i, const float* g, float* g_prev, const float* ce, float gl, int B,
+                   hipStream_t st) {
+  const zf_op_desc& op = t->desc.ops[i];
+  zf_trainer::NscBufs& nb = t->nsc[i];
+  const int D = t->D, dt = D / 2, r = t->rots[i];
+  return ce ? spline_bwd_launch<true>(t->sp[i], nb.P, g, 0.f, g_prev, nb.gP, B, D, dt, op.knots, r, ce, st)
+            : spline_bwd_launch<false>(t->sp[i], nb.P, g, gl, g_prev, nb.gP, B, D, dt, op.knots, r, nullptr, st);
+}
+
+// The reverse of one coupling's Dense chain, last layer first, from nb.gP =
+// d / d (raw spline parameters) to nb.gU = d / d Ubn.  gout (out_w wide) is
+// d / d (layer l's output); layer l's GEMM writes d / d (its input) through
+// the activation of layer l - 1 to gin: nb.gU for layer 0, else nb.gA / nb.gB
+// in turn.  wq (NULL: no weight gradients, trainer_vjp_chunk): before each
+// layer's GEMM, its dW_l = hin^T . gout and db_l = colsum(gout) are queued
+// into the fp64 gradient.
+int nsc_reverse_mlp(zf_trainer_t* t, int i, int B, long long Bg, WgradQueue* wq, hipStream_t st) {
+  const zf_op_desc& op = t->desc.ops[i];
+  zf_trainer::NscBufs& nb = t->nsc[i];
+  int dt, dc, DC, S;
+  nsc_dims(t, op, dt, dc, DC, S);
+  const float* gout = nb.gP;
+  int out_w = dt * S, which = 0, rc;
+  for (int l = op.n_hidden; l >= 0; --l) {
+    const int in_w = l == 0 ? DC : op.hidden[l - 1];
+    float* const gin = l == 0 ? nb.gU : (which ? nb.gB : nb.gA);
+    if (wq) {
+      const float* hin = l == 0 ? nb.Ubn : nb.H[l - 1];
+      // leaves capped by the split-K workspace (a power of two, the same on every rank)
+      const int cap = pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * out_w))));
+      rc = wgrad_deferred(*wq, in_w, out_w, B, leaves_for(B, Bg, t->comm.world, cap), hin, gout,
+                          t->d_g64 + op.off_w[l], t->d_g64 + op.off_b[l], t->d_ws, t->d_ws2, st);
+      if (rc) return rc;
+      if ((rc = wgrad_before_write(*wq, gin, st))) return rc;  // a deferred dW GEMM still reads it
+    }
+    rc = gemm(true, Bg, B, in_w, out_w, gout, out_w, t->d_nat + op.off_w[l], out_w, gin, in_w, st,
+              l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? nb.Z[l - 1] : nullptr, op.act,
+              t->splitq ? t->d_split : nullptr, kSplitFloats);
+    if (rc) return rc;
+    gout = gin;
+    out_w = in_w;
+    which ^= 1;
+  }
+  return ZF_OK;
+}
+
+// One coupling's BatchNorm scale / bias gradient from nb.gU = d / d Ubn: the
+// sums of gUbn and gUbn * Uhat over this rank's rows, leaves -> tree, copied
+// into the fp64 gradient.  The roots stay in d_roots ([0, DC): bias,
+// [DC, 2 DC): scale), where the train-mode reverse goes on with them.
+int bn_param_grads(zf_trainer_t* t, int i, const Leaves& lbn, int B, hipStream_t st) {
+  const zf_op_desc& op = t->desc.ops[i];
+  zf_trainer::NscBufs& nb = t->nsc[i];
+  int dt, dc, DC, S;
+  nsc_dims(t, op, dt, dc, DC, S);
+  double* gbn = t->d_g64 + op.off_bn;
+  hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, nb.gU, nb.Uhat, B,
+                     DC, lbn.rows, lbn.n, t->d_leaf);
+  ZF_CHECK_LAUNCH("leaf_colsums_kernel");
+  const int rc = launch_tree_cols(t->d_leaf, lbn.n, 2 * DC, t->d_roots, st, t->d_leaf2);
+  if (rc) return rc;
+  ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, t->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+  ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, t->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+  return ZF_OK;
+}
+
+// The reverse through one coupling's BatchNorm on the stored statistics (no
+// batch terms): gU = gUbn scale rstd on the rows whose mask entry is not zero,
+// its state columns added into g_out, its condition columns into gc (NULL:
+// none; gc_assign: stored, not added).
+int bn_eval_reverse(zf_trainer_t* t, int i, const float* mask, float* g_out, float* gc, int gc_assign, int B,
+                    hipStream_t st) {
+  const zf_op_desc& op = t->desc.ops[i];
+  zf_trainer::NscBufs& nb = t->nsc[i];
+  int dt, dc, DC, S;
+  nsc_dims(t, op, dt, dc, DC, S);
+  hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
+                     (const float*)(t->d_nat + op.off_bn + 2 * DC), (const float*)nb.rstd, mask, g_out, gc, gc_assign,
+                     B, t->D, t->C, dt, dc, t->rots[i]);
+  ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
+  return ZF_OK;
+}
+
+// A chain without a coupling met nothing that assigns gc: the pass's result does not depend on c.
+int gc_zero_unassigned(zf_trainer_t* t, float* gc, int gc_assign, int B, hipStream_t st) {
+  if (gc && gc_assign) ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * t->C * sizeof(float), st));
+  return ZF_OK;
+}
+
+// The latent's log-density of the rows in the last state on top of d_ld, with
+// nan_to_num (lp_out, or NULL); d_ce = cot (NULL: ones) where it is finite
+// before nan_to_num, 0 elsewhere; g_out = ce . d latent_lp / dz.
+int latent_vjp_launch(zf_trainer_t* t, int B, const float* cot, float* lp_out, float* g_out, hipStream_t st) {
+  const LatentConsts lc(t->desc);
+  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, t->sp[t->n_ops], t->d_ld, cot, B, t->D,
+                     t->rots[t->n_ops], lc.lt, lc.a, lc.betac, lc.tnm, lp_out, t->d_ce, g_out);
+  ZF_CHECK_LAUNCH("latent_vjp_kernel");
+  return ZF_OK;
+}
+
+// The end of a reverse pass: the fp64 gradient (all ranks' shares, tree over
+// ranks) -> fp32 G.  step_in_cast (one device, an (n)adamw update follows):
+// the cast also advances the optimiser's step counter.
+int close_gradient(zf_trainer_t* t, float* G, bool step_in_cast, hipStream_t st) {
+  const int W = t->comm.world;
+  if (W > 1) {
+    const int rc = t->comm.allgather(t->comm.ctx, t->d_g64, t->d_gath, (size_t)t->nat_floats * sizeof(double), st);
+    if (rc) return rc;
+#define ZF_L(NM) hipLaunchKernelGGL((tree_cols_cast_kernel<NM>), dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, \
+                                    (const double*)t->d_gath, W, (long long)t->nat_floats, G)
+    ZF_NMAX_DISPATCH(W, ZF_L);
+#undef ZF_L
+    ZF_CHECK_LAUNCH("tree_cols_cast_kernel");
+  } else {
+    hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, t->d_g64,
+                       (long long)t->nat_floats, G, step_in_cast ? t->d_bc : nullptr, t->opt.b1, t->opt.b2);
+    ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
+  }
+  return ZF_OK;
+}
+
+// ---- The forward passes ----
 
 // The train-mode forward of the staged batch of B rows (this rank's shard of a
 // global batch of Bg rows): batch statistics (exchanged over the ranks), the
@@ -444,13 +594,11 @@ int trainer_forward_train(zf_trainer_t* t, int B, long long Bg, int update_stats
   const std::vector<int>& rots = t->rots;
   auto state = [&](int i) { return t->sp[i]; };
   // a leading ShiftBounds sets ld itself (sb_forward_kernel, first)
-  if (desc.n_ops == 0 || desc.ops[0].kind != ZF_OP_SHIFT_BOUNDS)
-    ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
+  if (!t->sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
   const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
   // the single-block BatchNorm kernels have no exchange point (one device only)
   const bool small_ok = W == 1 && t->bn_small;
   int rc;
-  // ---- forward (train mode) ----
   for (int i = 0; i < desc.n_ops; ++i) {
     const zf_op_desc& op = desc.ops[i];
     if (op.kind == ZF_OP_ROLL) continue;  // an index rotation: rots[i + 1]
@@ -509,6 +657,72 @@ int trainer_forward_train(zf_trainer_t* t, int B, long long Bg, int update_stats
   return ZF_OK;
 }
 
+// The eval-mode forward of the staged batch of B rows (BatchNorm on the stored
+// mean / var, ShiftBounds on the stored bounds: rows are independent, nothing
+// is exchanged), activations kept in the arena, the log-det in d_ld.  Bg picks
+// the GEMM forms.  keep_uhat: also every coupling's nb.Uhat (zf_trainer_forward).
+int trainer_forward_eval(zf_trainer_t* t, int B, long long Bg, bool keep_uhat, hipStream_t st) {
+  const zf_flow_desc& desc = t->desc;
+  const std::vector<float*>& sp = t->sp;
+  if (!t->sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
+  int rc;
+  for (int i = 0; i < desc.n_ops; ++i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind == ZF_OP_ROLL) continue;  // an index rotation: rots[i + 1]
+    if (op.kind == ZF_OP_SHIFT_BOUNDS) {  // i == 0 (zf_trainer_create)
+      hipLaunchKernelGGL(sb_eval_fwd_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[i], sp[i + 1], t->d_ld,
+                         (const float*)(t->d_nat + op.off_sb), B, t->D);
+      ZF_CHECK_LAUNCH("sb_eval_fwd_kernel");
+    } else if (op.kind == ZF_OP_NSC) {
+      if ((rc = nsc_eval_conditioner(t, i, sp[i], keep_uhat, B, Bg, st))) return rc;
+      rc = spline_fwd_launch(sp[i], sp[i + 1], t->nsc[i].P, t->d_ld, B, t->D, t->D / 2, op.knots, t->rots[i], st);
+      if (rc) return rc;
+    } else {
+      return einval("op %d: unknown kind", i);
+    }
+  }
+  return ZF_OK;
+}
+
+// x = bijector.inverse(z, c) as a differentiable op (flow.py:76-77): eval mode
+// only, BatchNorm on the stored statistics (bijectors.py:367-371), ShiftBounds
+// on the stored bounds (:210-240).  The latent rows are staged in the last
+// state and the chain is walked from the last op to the first; for a coupling
+// the conditioning columns are the same on both sides, so the conditioner runs
+// on the op's input state of this pass (nsc_eval_conditioner, the eval
+// forward's own launches) and the spline inverse follows.  The states end up
+// where a forward pass on x would leave them, the activations in t->nsc[i];
+// d_ld collects every op's forward log-det at the inverse's own intermediate,
+// d_sm the row mask.
+int trainer_sample_forward(zf_trainer_t* t, int B, long long Bg, float* x_out, float* lq_out, hipStream_t st) {
+  const int D = t->D;
+  const zf_flow_desc& desc = t->desc;
+  const std::vector<float*>& sp = t->sp;
+  ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
+  ZF_TRY_HIP(hipMemsetAsync(t->d_sm, 0, (size_t)B * sizeof(float), st));
+  // the latent's log-density (on the zero log-det) and its finite flag; the gz
+  // output is rewritten by the reverse pass
+  int rc = latent_vjp_launch(t, B, nullptr, t->d_lq, t->d_g0, st);
+  if (rc) return rc;
+  for (int i = desc.n_ops - 1; i >= 0; --i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind == ZF_OP_ROLL || op.kind == ZF_OP_SHIFT_BOUNDS) continue;  // Roll: index map; ShiftBounds (first op): below
+    if (op.kind != ZF_OP_NSC) return einval("op %d: unknown kind", i);
+    if ((rc = nsc_eval_conditioner(t, i, sp[i + 1], true, B, Bg, st))) return rc;
+    rc = spline_inv_ld_launch(sp[i + 1], sp[i], t->nsc[i].P, t->d_ld, t->d_sm, B, D, D / 2, op.knots, t->rots[i], st);
+    if (rc) return rc;
+  }
+  return sb_eval_inv_launch(sp[t->sb_first ? 1 : 0], sp[0], x_out, t->sb_first ? t->d_nat + desc.ops[0].off_sb : nullptr,
+                            t->d_ld, t->d_lq, t->d_ce, t->d_sm, lq_out, B, D, st);
+}
+
+// ---- The reverse passes: seed, per coupling the spline's reverse,
+// nsc_reverse_mlp and the reverse through BatchNorm, then close_gradient.
+// The fp64 gradient needs no clearing per pass: every parameter entry is
+// assigned (the weight-gradient trees, the BatchNorm scale / bias gradients)
+// and the non-parameter entries (batch statistics, ShiftBounds rows) stay at
+// the zeros written once at zf_trainer_create ----
+
 // How trainer_reverse seeds and closes the reverse pass.
 struct ReverseArgs {
   bool rowce;         // d / d log_det of row b is d_ce[b] (else -1 / Bg for every row)
@@ -517,7 +731,119 @@ struct ReverseArgs {
   float* G;           // the fp32 gradient (blob layout)
   bool step_in_cast;  // one device, an (n)adamw update follows: the cast also steps
 };
-int trainer_reverse(zf_trainer_t* t, int B, long long Bg, const ReverseArgs& ra, hipStream_t st);
+
+// The reverse pass from d_g0 = d / d latent (and d_ce with ra.rowce) through
+// the activations a forward left in the arena, to the fp32 gradient ra.G: the
+// second half of trainer_body and of zf_trainer_backward.  ra.eval (the
+// forward ran on the stored statistics, nb.Uhat kept): the same spline
+// reverse, MLP reverse and BatchNorm scale / bias gradients; the reverse
+// through BatchNorm without its batch terms (bn_eval_reverse), so only the
+// gradient gather at the end exchanges anything over the ranks.
+int trainer_reverse(zf_trainer_t* t, int B, long long Bg, const ReverseArgs& ra, hipStream_t st) {
+  const int D = t->D, C = t->C, W = t->comm.world;
+  float* const gc = C > 0 ? ra.gc : nullptr;
+  const zf_flow_desc& desc = t->desc;
+  const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
+  const bool small_ok = W == 1 && t->bn_small && !ra.eval;
+  float* g = t->d_g0;
+  float* g_prev = t->d_g1;
+  int rc;
+  const float gl = -1.0f / (float)Bg;  // d loss / d log_det of every op and row
+  zf::WgradQueue wq;
+  wq.tb.count = 0;
+  wq.gq.count = 0;
+  int gc_assign = 1;  // the first coupling met (the last of the chain) assigns gc
+  for (int i = desc.n_ops - 1; i >= 0; --i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind == ZF_OP_ROLL || op.kind == ZF_OP_SHIFT_BOUNDS) continue;  // Roll: index map; SB: first op
+    int dt, dc, DC, S;
+    zf::nsc_dims(t, op, dt, dc, DC, S);
+    zf_trainer::NscBufs& nb = t->nsc[i];
+    const int r = t->rots[i];
+    if ((rc = spline_reverse(t, i, g, g_prev, ra.rowce ? t->d_ce : nullptr, gl, B, st))) return rc;
+    if ((rc = nsc_reverse_mlp(t, i, B, Bg, &wq, st))) return rc;
+    // BatchNorm: gU holds d loss / d Ubn
+    float* bn = t->d_nat + op.off_bn;
+    if (small_ok && (long long)B * DC <= zf::kBnSmall) {
+      double* gbn = t->d_g64 + op.off_bn;
+      hipLaunchKernelGGL(zf::bn_bwd_small, dim3(1), dim3(1024), 0, st, nb.gU, nb.Uhat, bn + 2 * DC, nb.rstd,
+                         gbn + 2 * DC, gbn + 3 * DC, g_prev, B, D, C, dt, dc, r, lbn.n, lbn.rows, gc, gc_assign);
+      ZF_CHECK_LAUNCH("bn_bwd_small");
+    } else if (ra.eval) {
+      // this rank's share of the scale / bias gradient (rows with ce == 0 hold zeros)
+      if ((rc = bn_param_grads(t, i, lbn, B, st))) return rc;
+      if ((rc = bn_eval_reverse(t, i, t->d_ce, g_prev, gc, gc_assign, B, st))) return rc;
+    } else {
+      // this rank's share of the scale / bias gradient; its roots -> (ranks) ->
+      // the reverse formula's global sums
+      if ((rc = bn_param_grads(t, i, lbn, B, st))) return rc;
+      if ((rc = dp_combine(t, t->d_roots, 2 * DC, st))) return rc;
+      // gU := d loss / d U, in place (reads each element before writing it)
+      hipLaunchKernelGGL(zf::bn_bwd_kernel, dim3(zf::blocks_for((int64_t)B * DC)), dim3(256), 0, st, nb.gU,
+                         nb.Uhat, bn + 2 * DC, nb.rstd, t->d_roots, t->d_roots + DC, nb.gU, B, Bg, DC);
+      ZF_CHECK_LAUNCH("bn_bwd_kernel");
+      hipLaunchKernelGGL(zf::scatter_gu_kernel, dim3(zf::blocks_for((int64_t)B * dc)), dim3(256), 0, st, nb.gU,
+                         g_prev, B, D, C, dt, dc, r);
+      ZF_CHECK_LAUNCH("scatter_gu_kernel");
+      if (gc) {
+        hipLaunchKernelGGL(zf::gather_gc_kernel, dim3(zf::blocks_for((int64_t)B * C)), dim3(256), 0, st, nb.gU, gc, B,
+                           C, dc, gc_assign);
+        ZF_CHECK_LAUNCH("gather_gc_kernel");
+      }
+    }
+    gc_assign = 0;
+    std::swap(g, g_prev);
+  }
+  if ((rc = zf::wgrad_flush(wq, st))) return rc;
+  if ((rc = gc_zero_unassigned(t, gc, gc_assign, B, st))) return rc;
+  return close_gradient(t, ra.G, ra.step_in_cast, st);
+}
+
+// trainer_sample_forward's reverse: from gx = d L / d x (and glq = d L / d log_q,
+// NULL: zeros) of this rank's rows to the fp32 gradient G, gz and gc.  Ops
+// from first to last: the spline inverse's reverse, then the ra.eval sequence
+// of trainer_reverse with the pass's row mask in place of ce.
+int trainer_sample_reverse(zf_trainer_t* t, int B, long long Bg, const float* gx, const float* glq, float* G,
+                           float* gz, float* gc_out, hipStream_t st) {
+  const int D = t->D;
+  float* const gc = t->C > 0 ? gc_out : nullptr;
+  const zf_flow_desc& desc = t->desc;
+  const std::vector<float*>& sp = t->sp;
+  const Leaves lbn = leaves_for(B, Bg, t->comm.world, kBnLeafCap);
+  int rc;
+  // d L / d log_q per row: where log_q is finite (latent_vjp_kernel's rule, on
+  // the whole chain's log-det) and the row counts; its share of gz
+  if (glq && (rc = latent_vjp_launch(t, B, glq, nullptr, t->d_gl, st))) return rc;
+  if ((rc = sample_mask_cot_launch(glq ? t->d_ce : nullptr, t->d_sm, t->d_ce, B, st))) return rc;
+  float* g = t->d_g0;
+  float* g_next = t->d_g1;
+  rc = sb_eval_inv_bwd_launch(sp[t->sb_first ? 1 : 0], gx, t->d_ce, t->d_sm,
+                              t->sb_first ? t->d_nat + desc.ops[0].off_sb : nullptr, g, B, D, st);
+  if (rc) return rc;
+  zf::WgradQueue wq;
+  wq.tb.count = 0;
+  wq.gq.count = 0;
+  int gc_assign = 1;  // the first coupling met assigns gc
+  for (int i = 0; i < desc.n_ops; ++i) {
+    const zf_op_desc& op = desc.ops[i];
+    if (op.kind != ZF_OP_NSC) continue;  // Roll: index map; ShiftBounds (first op): above
+    // spline: g (d / d state i) -> g_next (d / d state i + 1, transformed columns), gP
+    rc = spline_inv_bwd_launch(sp[i + 1], sp[i], t->nsc[i].P, g, t->d_ce, t->d_sm, g_next, t->nsc[i].gP, B, D, D / 2,
+                               op.knots, t->rots[i], st);
+    if (rc) return rc;
+    if ((rc = nsc_reverse_mlp(t, i, B, Bg, &wq, st))) return rc;
+    if ((rc = bn_param_grads(t, i, lbn, B, st))) return rc;
+    if ((rc = bn_eval_reverse(t, i, t->d_sm, g_next, gc, gc_assign, B, st))) return rc;
+    gc_assign = 0;
+    std::swap(g, g_next);
+  }
+  if ((rc = wgrad_flush(wq, st))) return rc;
+  if ((rc = gc_zero_unassigned(t, gc, gc_assign, B, st))) return rc;
+  if (gz && (rc = sample_gz_out_launch(g, glq ? t->d_gl : nullptr, t->d_sm, gz, B, D, t->rots[desc.n_ops], st))) return rc;
+  return close_gradient(t, G, false, st);
+}
+
+// ---- The whole passes ----
 
 // Train-mode forward + loss + reverse pass from the staged batch of B rows
 // (this rank's shard of a global batch of Bg rows); the loss lands in
@@ -580,132 +906,45 @@ int trainer_body(zf_trainer_t* t, const BatchArgs& a, float* G, bool step_in_cas
   return trainer_reverse(t, B, Bg, {weighted, false, a.gc, G, step_in_cast}, st);
 }
 
-// The reverse pass from d_g0 = d / d latent (and d_ce with ra.rowce) through
-// the activations a forward left in the arena, to the fp32 gradient ra.G: the
-// second half of trainer_body and of zf_trainer_backward.  ra.eval (the
-// forward ran on the stored statistics, nb.Uhat kept): the same spline
-// reverse, input-gradient GEMMs and deferred weight-gradient GEMMs; the
-// BatchNorm scale / bias gradients from the same leaf tree; the reverse
-// through BatchNorm without its batch terms (bn_eval_bwd_kernel), so only the
-// gradient gather at the end exchanges anything over the ranks.
-int trainer_reverse(zf_trainer_t* t, int B, long long Bg, const ReverseArgs& ra, hipStream_t st) {
-  const int D = t->D, C = t->C, W = t->comm.world;
-  float* const gc = C > 0 ? ra.gc : nullptr;
-  float* const G = ra.G;
-  const bool weighted = ra.rowce, step_in_cast = ra.step_in_cast;
+// Eval-mode forward with stored activations and the reverse pass for one
+// chunk of B <= bmax rows (zf_trainer_log_prob_vjp): the trainer's GEMMs and
+// spline kernels, none of its batch reductions, weight-gradient GEMMs, fp64
+// accumulators or optimiser.  The GEMM forms follow the chunk's row count
+// (never the other rows' values): a row's bits depend on its own inputs and
+// on how many rows share the chunk only.
+int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const float* cot, float* lp_out, float* gx,
+                      float* gc, int B, hipStream_t st) {
+  int rc = trainer_stage(t, x, c_in, nullptr, B, st);  // checked by zf_trainer_log_prob_vjp
+  if (rc) return rc;
+  const int D = t->D;
   const zf_flow_desc& desc = t->desc;
-  float* nat = t->d_nat;
-  double* G64 = t->d_g64;
-  const std::vector<int>& rots = t->rots;
-  auto state = [&](int i) { return t->sp[i]; };
-  const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
-  const bool small_ok = W == 1 && t->bn_small && !ra.eval;
+  if ((rc = trainer_forward_eval(t, B, B, false, st))) return rc;
+  // ---- latent, log_prob, the per-row cotangent ----
   float* g = t->d_g0;
   float* g_prev = t->d_g1;
-  int rc;
+  if ((rc = latent_vjp_launch(t, B, cot, lp_out, g, st))) return rc;
+  if (!gx && !gc) return ZF_OK;
   // ---- reverse ----
-  // G64 needs no clearing per step: every parameter entry is assigned below
-  // (the weight-gradient trees, the BatchNorm scale / bias gradients) and the
-  // non-parameter entries (batch statistics, ShiftBounds rows) stay at the
-  // zeros written once at zf_trainer_create
-  const float gl = -1.0f / (float)Bg;  // d loss / d log_det of every op and row
-  zf::WgradQueue wq;
-  wq.tb.count = 0;
-  wq.gq.count = 0;
-  int gc_assign = 1;  // the first coupling met (the last of the chain) assigns gc
+  int gc_assign = 1;
   for (int i = desc.n_ops - 1; i >= 0; --i) {
-    const zf_op_desc& op = desc.ops[i];
-    if (op.kind == ZF_OP_ROLL || op.kind == ZF_OP_SHIFT_BOUNDS) continue;  // Roll: index map; SB: first op
-    int dt, dc, DC, S;
-    zf::nsc_dims(t, op, dt, dc, DC, S);
-    zf_trainer::NscBufs& nb = t->nsc[i];
-    const int r = rots[i];
-    // spline: g -> g_prev (transformed columns), gP
-    rc = weighted
-             ? spline_bwd_launch<true>(state(i), nb.P, g, 0.f, g_prev, nb.gP, B, D, dt, op.knots, r, t->d_ce, st)
-             : spline_bwd_launch<false>(state(i), nb.P, g, gl, g_prev, nb.gP, B, D, dt, op.knots, r, nullptr, st);
-    if (rc) return rc;
-    // MLP reverse
-    DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
-    for (int l = op.n_hidden; l >= 0; --l) {
-      const int in_w = dg.in_w(l);
-      const float* hin = l == 0 ? nb.Ubn : nb.H[l - 1];
-      // dW_l = hin^T . gout ; db_l = colsum(gout): leaves capped by the
-      // split-K workspace (a power of two, the same on every rank)
-      const int cap = pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * dg.out_w))));
-      rc = zf::wgrad_deferred(wq, in_w, dg.out_w, B, leaves_for(B, Bg, W, cap), hin, dg.gout, G64 + op.off_w[l],
-                              G64 + op.off_b[l], t->d_ws, t->d_ws2, st);
-      if (rc) return rc;
-      if ((rc = zf::wgrad_before_write(wq, dg.gin(l), st))) return rc;  // a deferred dW GEMM still reads it
-      if ((rc = dg.layer(l, Bg, B, st))) return rc;
-    }
-    // BatchNorm: gU holds d loss / d Ubn
-    float* bn = nat + op.off_bn;
-    double* gbn = G64 + op.off_bn;
-    if (small_ok && (long long)B * DC <= zf::kBnSmall) {
-      hipLaunchKernelGGL(zf::bn_bwd_small, dim3(1), dim3(1024), 0, st, nb.gU, nb.Uhat, bn + 2 * DC, nb.rstd,
-                         gbn + 2 * DC, gbn + 3 * DC, g_prev, B, D, C, dt, dc, r, lbn.n, lbn.rows, gc, gc_assign);
-      ZF_CHECK_LAUNCH("bn_bwd_small");
-    } else if (ra.eval) {
-      // scale / bias gradients: this rank's share of the sums of gUbn * Uhat
-      // and gUbn (rows with ce == 0 hold zeros), then gU = gUbn scale rstd
-      hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, nb.gU,
-                         nb.Uhat, B, DC, lbn.rows, lbn.n, t->d_leaf);
-      ZF_CHECK_LAUNCH("leaf_colsums_kernel");
-      if ((rc = launch_tree_cols(t->d_leaf, lbn.n, 2 * DC, t->d_roots, st, t->d_leaf2))) return rc;
-      ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, t->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
-      ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, t->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
-                         (const float*)(bn + 2 * DC), (const float*)nb.rstd, (const float*)t->d_ce, g_prev, gc,
-                         gc_assign, B, D, C, dt, dc, r);
-      ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
-    } else {
-      // sums of gUbn and gUbn * Uhat: leaves -> tree (this rank's share of the
-      // scale / bias gradient) -> (ranks) -> the reverse formula's global sums
-      hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, nb.gU,
-                         nb.Uhat, B, DC, lbn.rows, lbn.n, t->d_leaf);
-      ZF_CHECK_LAUNCH("leaf_colsums_kernel");
-      if ((rc = launch_tree_cols(t->d_leaf, lbn.n, 2 * DC, t->d_roots, st, t->d_leaf2))) return rc;
-      ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, t->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
-      ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, t->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
-      if ((rc = dp_combine(t, t->d_roots, 2 * DC, st))) return rc;
-      // gU := d loss / d U, in place (reads each element before writing it)
-      hipLaunchKernelGGL(zf::bn_bwd_kernel, dim3(zf::blocks_for((int64_t)B * DC)), dim3(256), 0, st, nb.gU,
-                         nb.Uhat, bn + 2 * DC, nb.rstd, t->d_roots, t->d_roots + DC, nb.gU, B, Bg, DC);
-      ZF_CHECK_LAUNCH("bn_bwd_kernel");
-      hipLaunchKernelGGL(zf::scatter_gu_kernel, dim3(zf::blocks_for((int64_t)B * dc)), dim3(256), 0, st, nb.gU,
-                         g_prev, B, D, C, dt, dc, r);
-      ZF_CHECK_LAUNCH("scatter_gu_kernel");
-      if (gc) {
-        hipLaunchKernelGGL(zf::gather_gc_kernel, dim3(zf::blocks_for((int64_t)B * C)), dim3(256), 0, st, nb.gU, gc, B,
-                           C, dc, gc_assign);
-        ZF_CHECK_LAUNCH("gather_gc_kernel");
-      }
-    }
+    if (desc.ops[i].kind != ZF_OP_NSC) continue;  // Roll: index map; ShiftBounds (first op): below
+    if ((rc = spline_reverse(t, i, g, g_prev, t->d_ce, 0.f, B, st))) return rc;
+    if ((rc = nsc_reverse_mlp(t, i, B, B, nullptr, st))) return rc;
+    if ((rc = bn_eval_reverse(t, i, t->d_ce, g_prev, gc, gc_assign, B, st))) return rc;
     gc_assign = 0;
-    float* tmp = g;
-    g = g_prev;
-    g_prev = tmp;
+    std::swap(g, g_prev);
   }
-  if ((rc = zf::wgrad_flush(wq, st))) return rc;
-  if (gc && gc_assign)  // no coupling: the loss does not depend on c
-    ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * C * sizeof(float), st));
-  // ---- the gradient: (all ranks' fp64 shares, tree over ranks) -> fp32 ----
-  if (W > 1) {
-    rc = t->comm.allgather(t->comm.ctx, G64, t->d_gath, (size_t)t->nat_floats * sizeof(double), st);
-    if (rc) return rc;
-#define ZF_L(NM) hipLaunchKernelGGL((tree_cols_cast_kernel<NM>), dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, \
-                                    (const double*)t->d_gath, W, (long long)t->nat_floats, G)
-    ZF_NMAX_DISPATCH(W, ZF_L);
-#undef ZF_L
-    ZF_CHECK_LAUNCH("tree_cols_cast_kernel");
-  } else {
-    hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, G64,
-                       (long long)t->nat_floats, G, step_in_cast ? t->d_bc : nullptr, t->opt.b1, t->opt.b2);
-    ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
+  if ((rc = gc_zero_unassigned(t, gc, gc_assign, B, st))) return rc;
+  if (gx) {
+    hipLaunchKernelGGL(sb_eval_bwd_kernel, dim3(blocks_for((int64_t)B * D)), dim3(256), 0, st,
+                       (const float*)t->d_state, (const float*)g, (const float*)t->d_ce,
+                       t->sb_first ? (const float*)(t->d_nat + desc.ops[0].off_sb) : nullptr, gx, B, D);
+    ZF_CHECK_LAUNCH("sb_eval_bwd_kernel");
   }
   return ZF_OK;
 }
+
+// ---- The optimiser update, the captured step and the loss_grad / step entries ----
 
 // The chain's step (zf_optim.hip): the gradient is in t->d_grad, its cast did
 // not step (trainer_body without step_in_cast).
@@ -726,111 +965,6 @@ int trainer_update(zf_trainer_t* t, hipStream_t st, bool step_done = false) {
                      t->d_v, t->d_mask, (long long)t->nat_floats, o.learning_rate, o.b1, o.b2, o.eps, o.weight_decay,
                      o.nesterov, t->d_bc);
   ZF_CHECK_LAUNCH("adam_kernel");
-  return ZF_OK;
-}
-
-// The eval-mode forward of the staged batch of B rows (BatchNorm on the stored
-// mean / var, ShiftBounds on the stored bounds: rows are independent, nothing
-// is exchanged), activations kept in the arena, the log-det in d_ld.  Bg picks
-// the GEMM forms.  keep_uhat: also every coupling's nb.Uhat, which the
-// BatchNorm scale gradient reads (zf_trainer_forward; Ubn has the same bits).
-int trainer_forward_eval(zf_trainer_t* t, int B, long long Bg, bool keep_uhat, hipStream_t st) {
-  const int D = t->D, C = t->C;
-  const float* c = t->d_c;
-  const zf_flow_desc& desc = t->desc;
-  float* nat = t->d_nat;
-  const std::vector<float*>& sp = t->sp;
-  const std::vector<int>& rots = t->rots;
-  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
-  if (!sb_first) ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
-  int rc;
-  for (int i = 0; i < desc.n_ops; ++i) {
-    const zf_op_desc& op = desc.ops[i];
-    if (op.kind == ZF_OP_ROLL) continue;  // an index rotation: rots[i + 1]
-    const int rot = rots[i];
-    float* sin = sp[i];
-    float* sout = sp[i + 1];
-    if (op.kind == ZF_OP_SHIFT_BOUNDS) {  // i == 0 (zf_trainer_create)
-      hipLaunchKernelGGL(sb_eval_fwd_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sin, sout, t->d_ld,
-                         (const float*)(nat + op.off_sb), B, D);
-      ZF_CHECK_LAUNCH("sb_eval_fwd_kernel");
-    } else if (op.kind == ZF_OP_NSC) {
-      int dt, dc, DC, S;
-      nsc_dims(t, op, dt, dc, DC, S);
-      zf_trainer::NscBufs& nb = t->nsc[i];
-      if (keep_uhat) {
-        hipLaunchKernelGGL(bn_eval_fwd_uhat_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
-                           (const float*)(nat + op.off_bn), nb.Uhat, nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
-        ZF_CHECK_LAUNCH("bn_eval_fwd_uhat_kernel");
-      } else {
-        hipLaunchKernelGGL(bn_eval_fwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, sin, c,
-                           (const float*)(nat + op.off_bn), nb.Ubn, nb.rstd, B, D, C, dt, dc, rot);
-        ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
-      }
-      if ((rc = nsc_dense_fwd(t, op, nb, Bg, B, DC, dt * S, st))) return rc;
-      if ((rc = spline_fwd_launch(sin, sout, nb.P, t->d_ld, B, D, dt, op.knots, rot, st))) return rc;
-    } else {
-      return einval("op %d: unknown kind", i);
-    }
-  }
-  return ZF_OK;
-}
-
-// Eval-mode forward with stored activations and the reverse pass for one
-// chunk of B <= bmax rows (zf_trainer_log_prob_vjp): the trainer's GEMMs and
-// spline kernels, none of its batch reductions, weight-gradient GEMMs, fp64
-// accumulators or optimiser.  The GEMM forms follow the chunk's row count
-// (never the other rows' values): a row's bits depend on its own inputs and
-// on how many rows share the chunk only.
-int trainer_vjp_chunk(zf_trainer_t* t, const float* x, const float* c_in, const float* cot, float* lp_out, float* gx,
-                      float* gc, int B, hipStream_t st) {
-  int rc = trainer_stage(t, x, c_in, nullptr, B, st);  // checked by zf_trainer_log_prob_vjp
-  if (rc) return rc;
-  const int D = t->D, C = t->C;
-  const zf_flow_desc& desc = t->desc;
-  float* nat = t->d_nat;
-  const std::vector<float*>& sp = t->sp;
-  const std::vector<int>& rots = t->rots;
-  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
-  if ((rc = trainer_forward_eval(t, B, B, false, st))) return rc;
-  // ---- latent, log_prob, the per-row cotangent ----
-  const LatentConsts lc(desc);
-  float* g = t->d_g0;
-  float* g_prev = t->d_g1;
-  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, cot, B, D,
-                     rots[desc.n_ops], lc.lt, lc.a, lc.betac, lc.tnm, lp_out, t->d_ce, g);
-  ZF_CHECK_LAUNCH("latent_vjp_kernel");
-  if (!gx && !gc) return ZF_OK;
-  // ---- reverse ----
-  int gc_assign = 1;
-  for (int i = desc.n_ops - 1; i >= 0; --i) {
-    const zf_op_desc& op = desc.ops[i];
-    if (op.kind != ZF_OP_NSC) continue;  // Roll: index map; ShiftBounds (first op): below
-    int dt, dc, DC, S;
-    nsc_dims(t, op, dt, dc, DC, S);
-    zf_trainer::NscBufs& nb = t->nsc[i];
-    const int r = rots[i];
-    rc = spline_bwd_launch<true>(sp[i], nb.P, g, 0.f, g_prev, nb.gP, B, D, dt, op.knots, r, t->d_ce, st);
-    if (rc) return rc;
-    DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
-    for (int l = op.n_hidden; l >= 0; --l)
-      if ((rc = dg.layer(l, B, B, st))) return rc;
-    const float* bn = nat + op.off_bn;
-    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
-                       bn + 2 * DC, (const float*)nb.rstd, (const float*)t->d_ce, g_prev, gc, gc_assign, B, D, C, dt,
-                       dc, r);
-    ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
-    gc_assign = 0;
-    std::swap(g, g_prev);
-  }
-  if (gc && gc_assign)  // no coupling: log_prob does not depend on c
-    ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * C * sizeof(float), st));
-  if (gx) {
-    hipLaunchKernelGGL(sb_eval_bwd_kernel, dim3(blocks_for((int64_t)B * D)), dim3(256), 0, st,
-                       (const float*)t->d_state, (const float*)g, (const float*)t->d_ce,
-                       sb_first ? (const float*)(nat + desc.ops[0].off_sb) : nullptr, gx, B, D);
-    ZF_CHECK_LAUNCH("sb_eval_bwd_kernel");
-  }
   return ZF_OK;
 }
 
@@ -878,7 +1012,7 @@ inline int copy_loss(zf_trainer_t* t, const BatchArgs& a) {
 
 // Every zf_trainer_loss_grad* entry: the loss and its gradient (and gc).
 int run_loss_grad(zf_trainer_t* t, const BatchArgs& a) {
-  t->pend_mode = kPendNone;  // the arena is about to be overwritten
+  set_pending(t, kPendNone);  // the arena is about to be overwritten
   int rc = check_batch(t, a);
   if (!rc) rc = trainer_stage(t, a.x, a.c, a.w, a.rows, a.stream);
   if (!rc) rc = trainer_body(t, a, a.grad ? a.grad : t->d_grad, false);
@@ -890,7 +1024,7 @@ int run_loss_grad(zf_trainer_t* t, const BatchArgs& a) {
 // or with a communicator, launches the same kernels in the same order
 // eagerly, so the same bits (tests/test_gpu_train.py::test_step_graph_matches_eager).
 int run_step(zf_trainer_t* t, const BatchArgs& a) {
-  t->pend_mode = kPendNone;
+  set_pending(t, kPendNone);
   int rc = check_batch(t, a);
   if (!rc) rc = trainer_stage(t, a.x, a.c, a.w, a.rows, a.stream);
   if (rc) return rc;
@@ -909,156 +1043,14 @@ int run_step(zf_trainer_t* t, const BatchArgs& a) {
   return copy_loss(t, a);
 }
 
-// ---- gradients through sampling -------------------------------------------------
-// x = bijector.inverse(z, c) as a differentiable op (flow.py:76-77): eval mode
-// only, BatchNorm on the stored statistics (bijectors.py:367-371), ShiftBounds
-// on the stored bounds (:210-240).  The latent rows are staged in the last
-// state and the chain is walked from the last op to the first; for a coupling
-// the conditioning columns are the same on both sides, so the conditioner runs
-// on the op's input state of this pass (bn_eval_fwd_uhat_kernel +
-// nsc_dense_fwd, the eval forward's own launches) and the spline inverse
-// follows.  The states end up where a forward pass on x would leave them, the
-// activations in t->nsc[i]; d_ld collects every op's forward log-det at the
-// inverse's own intermediate, d_sm the row mask.
-int trainer_sample_forward(zf_trainer_t* t, int B, long long Bg, float* x_out, float* lq_out, hipStream_t st) {
-  const int D = t->D, C = t->C;
-  const zf_flow_desc& desc = t->desc;
-  float* nat = t->d_nat;
-  const std::vector<float*>& sp = t->sp;
-  const std::vector<int>& rots = t->rots;
-  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
-  ZF_TRY_HIP(hipMemsetAsync(t->d_ld, 0, (size_t)B * sizeof(float), st));
-  ZF_TRY_HIP(hipMemsetAsync(t->d_sm, 0, (size_t)B * sizeof(float), st));
-  // the latent's log-density (on the zero log-det) and its finite flag; the gz
-  // output is rewritten by the reverse pass
-  const LatentConsts lc(desc);
-  hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld,
-                     (const float*)nullptr, B, D, rots[desc.n_ops], lc.lt, lc.a, lc.betac, lc.tnm, t->d_lq, t->d_ce,
-                     t->d_g0);
-  ZF_CHECK_LAUNCH("latent_vjp_kernel");
-  int rc;
-  for (int i = desc.n_ops - 1; i >= 0; --i) {
-    const zf_op_desc& op = desc.ops[i];
-    if (op.kind == ZF_OP_ROLL || op.kind == ZF_OP_SHIFT_BOUNDS) continue;  // Roll: index map; ShiftBounds (first op): below
-    if (op.kind != ZF_OP_NSC) return einval("op %d: unknown kind", i);
-    int dt, dc, DC, S;
-    nsc_dims(t, op, dt, dc, DC, S);
-    zf_trainer::NscBufs& nb = t->nsc[i];
-    const int rot = rots[i];
-    hipLaunchKernelGGL(bn_eval_fwd_uhat_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st,
-                       (const float*)sp[i + 1], (const float*)t->d_c, (const float*)(nat + op.off_bn), nb.Uhat, nb.Ubn,
-                       nb.rstd, B, D, C, dt, dc, rot);
-    ZF_CHECK_LAUNCH("bn_eval_fwd_uhat_kernel");
-    if ((rc = nsc_dense_fwd(t, op, nb, Bg, B, DC, dt * S, st))) return rc;
-    if ((rc = spline_inv_ld_launch(sp[i + 1], sp[i], nb.P, t->d_ld, t->d_sm, B, D, dt, op.knots, rot, st))) return rc;
-  }
-  return sb_eval_inv_launch(sp[sb_first ? 1 : 0], sp[0], x_out, sb_first ? nat + desc.ops[0].off_sb : nullptr, t->d_ld,
-                            t->d_lq, t->d_ce, t->d_sm, lq_out, B, D, st);
-}
-
-// Its reverse: from gx = d L / d x (and glq = d L / d log_q, NULL: zeros) of
-// this rank's rows to the fp32 gradient G, gz and gc.  Ops from first to
-// last: the spline inverse's reverse, then the ra.eval sequence of
-// trainer_reverse on the same helpers (input-gradient GEMMs, deferred
-// weight-gradient GEMMs, the BatchNorm scale / bias gradients from the leaf
-// tree, bn_eval_bwd_kernel with the pass's row mask in place of ce), the same
-// cast and rank exchange.  G64 needs no clearing, as there.
-int trainer_sample_reverse(zf_trainer_t* t, int B, long long Bg, const float* gx, const float* glq, float* G,
-                           float* gz, float* gc_out, hipStream_t st) {
-  const int D = t->D, C = t->C, W = t->comm.world;
-  float* const gc = C > 0 ? gc_out : nullptr;
-  const zf_flow_desc& desc = t->desc;
-  float* nat = t->d_nat;
-  double* G64 = t->d_g64;
-  const std::vector<float*>& sp = t->sp;
-  const std::vector<int>& rots = t->rots;
-  const bool sb_first = desc.n_ops > 0 && desc.ops[0].kind == ZF_OP_SHIFT_BOUNDS;
-  const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
-  int rc;
-  // d L / d log_q per row: where log_q is finite (latent_vjp_kernel's rule, on
-  // the whole chain's log-det) and the row counts; its share of gz
-  if (glq) {
-    const LatentConsts lc(desc);
-    hipLaunchKernelGGL(latent_vjp_kernel, dim3(blocks_for(B)), dim3(256), 0, st, sp[desc.n_ops], t->d_ld, glq, B, D,
-                       rots[desc.n_ops], lc.lt, lc.a, lc.betac, lc.tnm, (float*)nullptr, t->d_ce, t->d_gl);
-    ZF_CHECK_LAUNCH("latent_vjp_kernel");
-  }
-  if ((rc = sample_mask_cot_launch(glq ? t->d_ce : nullptr, t->d_sm, t->d_ce, B, st))) return rc;
-  float* g = t->d_g0;
-  float* g_next = t->d_g1;
-  rc = sb_eval_inv_bwd_launch(sp[sb_first ? 1 : 0], gx, t->d_ce, t->d_sm,
-                              sb_first ? nat + desc.ops[0].off_sb : nullptr, g, B, D, st);
-  if (rc) return rc;
-  zf::WgradQueue wq;
-  wq.tb.count = 0;
-  wq.gq.count = 0;
-  int gc_assign = 1;  // the first coupling met assigns gc
-  for (int i = 0; i < desc.n_ops; ++i) {
-    const zf_op_desc& op = desc.ops[i];
-    if (op.kind != ZF_OP_NSC) continue;  // Roll: index map; ShiftBounds (first op): above
-    int dt, dc, DC, S;
-    nsc_dims(t, op, dt, dc, DC, S);
-    zf_trainer::NscBufs& nb = t->nsc[i];
-    const int r = rots[i];
-    // spline: g (d / d state i) -> g_next (d / d state i + 1, transformed columns), gP
-    rc = spline_inv_bwd_launch(sp[i + 1], sp[i], nb.P, g, t->d_ce, t->d_sm, g_next, nb.gP, B, D, dt, op.knots, r, st);
-    if (rc) return rc;
-    DgradChain dg{t, op, nb, DC, nb.gP, dt * S};
-    for (int l = op.n_hidden; l >= 0; --l) {
-      const int in_w = dg.in_w(l);
-      const float* hin = l == 0 ? nb.Ubn : nb.H[l - 1];
-      const int cap = pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * dg.out_w))));
-      rc = wgrad_deferred(wq, in_w, dg.out_w, B, leaves_for(B, Bg, W, cap), hin, dg.gout, G64 + op.off_w[l],
-                          G64 + op.off_b[l], t->d_ws, t->d_ws2, st);
-      if (rc) return rc;
-      if ((rc = wgrad_before_write(wq, dg.gin(l), st))) return rc;
-      if ((rc = dg.layer(l, Bg, B, st))) return rc;
-    }
-    float* bn = nat + op.off_bn;
-    double* gbn = G64 + op.off_bn;
-    hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, nb.gU, nb.Uhat, B,
-                       DC, lbn.rows, lbn.n, t->d_leaf);
-    ZF_CHECK_LAUNCH("leaf_colsums_kernel");
-    if ((rc = launch_tree_cols(t->d_leaf, lbn.n, 2 * DC, t->d_roots, st, t->d_leaf2))) return rc;
-    ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, t->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
-    ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, t->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)nb.gU,
-                       (const float*)(bn + 2 * DC), (const float*)nb.rstd, (const float*)t->d_sm, g_next, gc, gc_assign,
-                       B, D, C, dt, dc, r);
-    ZF_CHECK_LAUNCH("bn_eval_bwd_kernel");
-    gc_assign = 0;
-    std::swap(g, g_next);
-  }
-  if ((rc = wgrad_flush(wq, st))) return rc;
-  if (gc && gc_assign)  // no coupling: x does not depend on c
-    ZF_TRY_HIP(hipMemsetAsync(gc, 0, (size_t)B * C * sizeof(float), st));
-  if (gz && (rc = sample_gz_out_launch(g, glq ? t->d_gl : nullptr, t->d_sm, gz, B, D, rots[desc.n_ops], st))) return rc;
-  // ---- the gradient: (all ranks' fp64 shares, tree over ranks) -> fp32, as trainer_reverse ----
-  if (W > 1) {
-    rc = t->comm.allgather(t->comm.ctx, G64, t->d_gath, (size_t)t->nat_floats * sizeof(double), st);
-    if (rc) return rc;
-#define ZF_L(NM) hipLaunchKernelGGL((tree_cols_cast_kernel<NM>), dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, \
-                                    (const double*)t->d_gath, W, (long long)t->nat_floats, G)
-    ZF_NMAX_DISPATCH(W, ZF_L);
-#undef ZF_L
-    ZF_CHECK_LAUNCH("tree_cols_cast_kernel");
-  } else {
-    hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(t->nat_floats)), dim3(256), 0, st, G64,
-                       (long long)t->nat_floats, G, (float*)nullptr, t->opt.b1, t->opt.b2);
-    ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
-  }
-  return ZF_OK;
-}
-
 // ZF_EINVAL while a ShiftBounds dim that maps through the stored xmin / xmax
 // still holds the initial +-inf (no train-mode pass has run): its inverse is
 // undefined.  Read back once; training only widens finite bounds.
 int check_sample_bounds(zf_trainer_t* t, hipStream_t st) {
-  const zf_flow_desc& desc = t->desc;
-  if (t->sb_ok || desc.n_ops == 0 || desc.ops[0].kind != ZF_OP_SHIFT_BOUNDS) return ZF_OK;
+  if (t->sb_ok || !t->sb_first) return ZF_OK;
   std::vector<float> rows((size_t)8 * t->D);
   ZF_TRY_HIP(hipStreamSynchronize(st));
-  ZF_TRY_HIP(hipMemcpy(rows.data(), t->d_nat + desc.ops[0].off_sb, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
+  ZF_TRY_HIP(hipMemcpy(rows.data(), t->d_nat + t->desc.ops[0].off_sb, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (int j = 0; j < t->D; ++j) {
     if ((int)rows[8 * j] == ZF_SB_BOTH) continue;
     if (!std::isfinite(rows[8 * j + 3]) || !std::isfinite(rows[8 * j + 4]))
@@ -1131,12 +1123,11 @@ int zf_trainer_step(zf_trainer_t* t, const float* x, const float* c, int64_t B, 
 int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, const float* cot, float* log_prob,
                             float* gx, float* gc, int64_t N, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  t->pend_mode = zf::kPendNone;
-  if (N < 1) return zf::einval("N must be at least 1");
-  if (!x) return zf::einval("x is NULL");
-  if (t->C > 0 && !c) return zf::einval("flow is conditional but c is NULL");
-  if (t->desc.latent == ZF_LATENT_NONE) return zf::einval("flow has no latent distribution");
+  zf::set_pending(t, zf::kPendNone);
   hipStream_t st = (hipStream_t)stream;
+  const int rc0 = zf::check_batch(t, {x, c, nullptr, N, N, 0, nullptr, nullptr, nullptr, st}, zf::kBatchChunked);
+  if (rc0) return rc0;
+  if (t->desc.latent == ZF_LATENT_NONE) return zf::einval("flow has no latent distribution");
   const int D = t->D, C = t->C;
   for (int64_t off = 0; off < N; off += t->bmax) {
     const int B = (int)std::min<int64_t>(t->bmax, N - off);
@@ -1155,7 +1146,7 @@ int zf_trainer_log_prob_vjp(zf_trainer_t* t, const float* x, const float* c, con
 int zf_trainer_forward(zf_trainer_t* t, const float* x, const float* c, int64_t rows, int64_t global_rows, int train,
                        int update_stats, float* log_prob, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  t->pend_mode = zf::kPendNone;
+  zf::set_pending(t, zf::kPendNone);
   hipStream_t st = (hipStream_t)stream;
   const int rc0 = zf::check_batch(t, {x, c, nullptr, rows, global_rows, update_stats, nullptr, nullptr, nullptr, st});
   if (rc0) return rc0;
@@ -1169,14 +1160,8 @@ int zf_trainer_forward(zf_trainer_t* t, const float* x, const float* c, int64_t 
                : zf::trainer_forward_eval(t, B, global_rows, true, st);
   if (rc) return rc;
   // log_prob with nan_to_num; its ce / gz outputs are rewritten by backward's launch
-  const zf::LatentConsts lc(t->desc);
-  hipLaunchKernelGGL(zf::latent_vjp_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, t->sp[t->n_ops], t->d_ld,
-                     (const float*)nullptr, B, t->D, t->rots[t->n_ops], lc.lt, lc.a, lc.betac, lc.tnm, log_prob,
-                     t->d_ce, t->d_g0);
-  ZF_CHECK_LAUNCH("latent_vjp_kernel");
-  t->pend_mode = train ? zf::kPendTrain : zf::kPendEval;
-  t->pend_rows = rows;
-  t->pend_global = global_rows;
+  if ((rc = zf::latent_vjp_launch(t, B, nullptr, log_prob, t->d_g0, st))) return rc;
+  zf::set_pending(t, train ? zf::kPendTrain : zf::kPendEval, rows, global_rows);
   return ZF_OK;
 }
 
@@ -1185,20 +1170,19 @@ int zf_trainer_backward(zf_trainer_t* t, const float* cot, float* grad, float* g
   if (t->pend_mode != zf::kPendTrain && t->pend_mode != zf::kPendEval)  // a sampling pass is not a forward
     return zf::einval("no forward pending");
   const bool eval = t->pend_mode == zf::kPendEval;
-  t->pend_mode = zf::kPendNone;  // one backward per forward
-  hipStream_t st = (hipStream_t)stream;
   const int B = (int)t->pend_rows;
+  const long long Bg = t->pend_global;
+  zf::set_pending(t, zf::kPendNone);  // one backward per forward
+  hipStream_t st = (hipStream_t)stream;
   // ce = cot where log_prob is finite before nan_to_num (0 elsewhere), gz = ce . d latent_lp / dz
-  const zf::LatentConsts lc(t->desc);
-  hipLaunchKernelGGL(zf::latent_vjp_kernel, dim3(zf::blocks_for(B)), dim3(256), 0, st, t->sp[t->n_ops], t->d_ld, cot,
-                     B, t->D, t->rots[t->n_ops], lc.lt, lc.a, lc.betac, lc.tnm, (float*)nullptr, t->d_ce, t->d_g0);
-  ZF_CHECK_LAUNCH("latent_vjp_kernel");
-  return zf::trainer_reverse(t, B, t->pend_global, {true, eval, gc, grad ? grad : t->d_grad, false}, st);
+  const int rc = zf::latent_vjp_launch(t, B, cot, nullptr, t->d_g0, st);
+  if (rc) return rc;
+  return zf::trainer_reverse(t, B, Bg, {true, eval, gc, grad ? grad : t->d_grad, false}, st);
 }
 
 int zf_trainer_apply_gradient(zf_trainer_t* t, const float* grad, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  t->pend_mode = zf::kPendNone;
+  zf::set_pending(t, zf::kPendNone);
   hipStream_t st = (hipStream_t)stream;
   if (grad && grad != t->d_grad)
     ZF_TRY_HIP(hipMemcpyAsync(t->d_grad, grad, (size_t)t->nat_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1212,29 +1196,19 @@ int zf_trainer_apply_gradient(zf_trainer_t* t, const float* grad, void* stream) 
 int zf_trainer_sample_forward(zf_trainer_t* t, const float* z, const float* c, int64_t rows, int64_t global_rows,
                               float* x, float* log_q, void* stream) {
   if (!t) return zf::einval("trainer is NULL");
-  t->pend_mode = zf::kPendNone;
+  zf::set_pending(t, zf::kPendNone);
   hipStream_t st = (hipStream_t)stream;
-  // check_batch's rules, but for global_rows on one device: the pass has no
-  // batch statistics, so there a larger global_rows only declares the rows a
-  // micro-batch of that batch (it picks the GEMM forms and the leaf layout)
-  if (rows < 1 || rows > t->bmax)
-    return zf::einval("batch %lld outside [1, %lld]", (long long)rows, (long long)t->bmax);
-  if (!z) return zf::einval("z is NULL");
-  if (t->C > 0 && !c) return zf::einval("flow is conditional but c is NULL");
-  if (global_rows < rows)
-    return zf::einval("global_rows %lld vs rows %lld (world %d)", (long long)global_rows, (long long)rows, t->comm.world);
+  int rc = zf::check_batch(t, {z, c, nullptr, rows, global_rows, 0, nullptr, nullptr, nullptr, st}, zf::kBatchSample);
+  if (rc) return rc;
   if (!x) return zf::einval("x is NULL");
   if (t->desc.latent == ZF_LATENT_NONE) return zf::einval("flow has no latent distribution");
-  int rc = zf::check_sample_bounds(t, st);
-  if (rc) return rc;
+  if ((rc = zf::check_sample_bounds(t, st))) return rc;
   const int B = (int)rows;
   if (t->C > 0)
     ZF_TRY_HIP(hipMemcpyAsync(t->d_c, c, (size_t)rows * t->C * sizeof(float), hipMemcpyDeviceToDevice, st));
   if ((rc = zf::sample_rot_in_launch(z, t->sp[t->n_ops], B, t->D, t->rots[t->n_ops], st))) return rc;
   if ((rc = zf::trainer_sample_forward(t, B, global_rows, x, log_q, st))) return rc;
-  t->pend_mode = zf::kPendSample;
-  t->pend_rows = rows;
-  t->pend_global = global_rows;
+  zf::set_pending(t, zf::kPendSample, rows, global_rows);
   return ZF_OK;
 }
 
@@ -1243,9 +1217,10 @@ int zf_trainer_sample_backward(zf_trainer_t* t, const float* gx, const float* gl
   if (!t) return zf::einval("trainer is NULL");
   if (t->pend_mode != zf::kPendSample) return zf::einval("no forward pending");
   if (!gx) return zf::einval("gx is NULL");
-  t->pend_mode = zf::kPendNone;  // one backward per forward
-  return zf::trainer_sample_reverse(t, (int)t->pend_rows, t->pend_global, gx, glq, grad ? grad : t->d_grad, gz, gc,
-                                    (hipStream_t)stream);
+  const int B = (int)t->pend_rows;
+  const long long Bg = t->pend_global;
+  zf::set_pending(t, zf::kPendNone);  // one backward per forward
+  return zf::trainer_sample_reverse(t, B, Bg, gx, glq, grad ? grad : t->d_grad, gz, gc, (hipStream_t)stream);
 }
 
 int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
@@ -1257,7 +1232,7 @@ int zf_trainer_get_blob(zf_trainer_t* t, float* blob_host) {
 
 int zf_trainer_set_blob(zf_trainer_t* t, const float* blob_host) {
   if (!t || !blob_host) return zf::einval("NULL argument");
-  t->pend_mode = zf::kPendNone;
+  zf::set_pending(t, zf::kPendNone);
   t->sb_ok = false;
   ZF_TRY_HIP(hipDeviceSynchronize());
   ZF_TRY_HIP(hipMemcpy(t->d_nat, blob_host, t->nat_floats * sizeof(float), hipMemcpyHostToDevice));
@@ -1339,7 +1314,7 @@ extern "C" {
 
 int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, const unsigned char* decay_mask) {
   if (!t || !chain) return zf::einval("NULL argument");
-  t->pend_mode = zf::kPendNone;
+  zf::set_pending(t, zf::kPendNone);
   const int S = chain->n_stages;
   if (S < 1) return zf::einval("optimiser chain: no stage");
   if (S > ZF_OPT_MAX_STAGES)
