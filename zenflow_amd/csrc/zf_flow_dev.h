@@ -5,6 +5,7 @@
 // BatchNorm + first Dense layer, the latent log_prob epilogue).
 #pragma once
 #include "zf_act.h"
+#include "zf_flow_image.h"
 #include "zf_internal.h"
 #include "zf_random.h"
 #include "zf_spline.h"
@@ -18,57 +19,6 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = 32;  // samples per wave (one MFMA column block)
-constexpr int kMaxOps = 64;
-
-struct DevOp {
-  int kind, shift, K, S;
-  int n_hidden, dt, dc, DC;
-  int KS0, T_last, nslot_mask, act;
-  long long w[17];
-  long long b[17];
-  long long bn;
-  long long sb;
-  long long first_chunk;  // blob offset of this NSC's first streamed weight chunk (fp32 kernel)
-  // bf16x3 kernel: byte offset of this NSC's weight-group stream in the x3
-  // blob, its group count, blob offset of the row-permuted last-layer bias,
-  // and the next NSC op index in forward / inverse execution order (or -1).
-  long long x3;
-  long long x3_blast;
-  int x3_groups, x3_tlast;
-  int x3_next[2];
-  int x3_kw[17];  // f16x2: power-of-two weight scale of streamed layer l (1..n_hidden)
-  // f16x2 swish: per Dense_l (0..n_hidden-1, as packed: log2(e) prescale
-  // included) R = max_j sum_k |W[k][j]| and B = max_j |b[j]|, so every
-  // pre-activation |v_j| <= R * max_k |a_k| + B (x3_early_scale)
-  float x3_rb[16][2];
-  // split-MFMA kernel: this NSC's small parameters (BatchNorm, Dense_0,
-  // biases, the permuted last bias) are the contiguous blob floats
-  // [bn, bn + 256 * x3_par_pieces), DMA'd into LDS one NSC ahead
-  int x3_par_pieces;
-  // the next NSC in forward / inverse execution order (x3_next[d] >= 0):
-  // its group-0 byte offset and pieces, its parameter block and pieces —
-  // copied here so the kernel's per-NSC scalars are one batch of independent loads
-  long long x3_nbase[2], x3_nbn[2];
-  int x3_npieces[2], x3_npar[2];
-};
-
-struct DevFlow {
-  int D, C, latent, n_ops;
-  int HP, nslot, per_wave, x3_ok;
-  int small_floats;  // packed blob [0, small_floats): per-op small parameters
-  int x3_par_bytes;  // split-MFMA kernel: LDS bytes of one NSC's small-parameter region (max over NSCs)
-  int kreal;  // split-MFMA kernels: the couplings' knot count (the kernel's K may be padded above it)
-  int _pad;
-  float lat_c0, lat_c1, lat_c2, lat_c3;
-  DevOp ops[kMaxOps];
-  // softmax_with_threshold's constants of every coupling's K (KnotConsts: c,
-  // norm, rnorm, 0), formed on the device once at zf_flow_create
-  // (knot_consts_kernel) so that the resident form does not divide in fp64
-  // per tile.  Behind the ops: their stride, which every
-  // kernel's code holds as a literal, stays what it was.
-  float kc[kMaxOps][4];
-};
-
 __device__ __forceinline__ void wave_lds_sync() {
   // LDS ops of one wave execute in order; this only stops the compiler from
   // moving LDS accesses across the exchange point.
@@ -355,23 +305,6 @@ __device__ __forceinline__ void flow_epilogue(const DevFlow* __restrict__ F, con
   flow_out_rows(xs, s, hh, rot, D, row, valid, ld, y_out, ld_out);
 }
 
-// The coupling as the resident form's specialised frame runs it (x3_nsc LIT):
-// D = 4, C = 0 (dt = dc = DC = 2, one layer-0 k-step), hidden 128 with one
-// streamed hidden layer, swish, and exactly K real knots.  The shape fixes the
-// layout of the small-parameter region (zf_flow_create: BatchNorm rows,
-// Dense_0, the biases, the permuted last bias), so its offsets are literals
-// (float offsets from op.bn; the host checks them against the handle's,
-// x3_resident_fits), and what is left of the op's scalars — the layer scales,
-// the bound pairs and the knot constants — is read once per pass, not per tile.
-struct X3Lit {
-  static constexpr int kW0 = 8;                 // Dense_0 fragments, behind the 3 x 2 BatchNorm rows
-  static constexpr int kB0 = kW0 + 4 * 64;      // Dense_0's bias; the hidden bias follows it
-  static constexpr int blast(int K) { return kB0 + 2 * 128 + (2 * (3 * K - 1) + 31) / 32 * 32; }
-  float bc, rnorm;  // KnotConsts: c * rnorm, rnorm (both resident frames carry these two through a pass)
-  float rb[2][2];   // DevOp::x3_rb of Dense_0 and Dense_1
-  int kw1, kw_last;
-};
-
 // Host-side entry of the bf16x3 kernel (zf_flow_x3.hip).
 struct X3Launch {
   const DevFlow* desc;
@@ -414,7 +347,6 @@ int launch_flow_x3(const X3Launch& a, bool inverse);
 // and whether a call of this shape can run it (fills res_blocks / res_slots / res_span).
 int x3_resident_mode();
 bool x3_resident_fits(const zf_flow_desc& desc, X3Launch& a, bool inverse, int ncu);
-bool x3_eligible(const zf_flow_desc& desc, int HP, int* K);
 // Layered eval path (zf_layered.hip) for shapes the fused kernels cannot hold
 // (a hidden width above 256): op by op over row chunks — BatchNorm, the Dense
 // layers on the trainer's GEMMs, the per-(row, dim) spline kernels.
@@ -424,13 +356,5 @@ void layered_destroy(LayeredFlow* L);
 int layered_run(LayeredFlow* L, const DevFlow& F, const float* packed, bool inverse, int op_begin, int op_end,
                 const float* x, const float* c, float* y, const float* ld_in, float* ld_out, float* lp, double* part,
                 long long N, hipStream_t st, unsigned long long seed, int gen);
-int x3_last_tiles(int K);
-int x3_pairs(const zf_flow_desc& desc);
-int x3_buf_tiles(const zf_flow_desc& desc, int T, int K);
-size_t x3_lds_bytes(int TB, int D, int NT, int par_bytes);
-int x3_scheme();
-int x3_scheme_for(const zf_flow_desc& desc);
-void x3_pack(const zf_flow_desc& desc, const float* nat, int T, int NT, int Kp, DevFlow& F, float* packed,
-             std::vector<uint16_t>& stream);
 
 }  // namespace zf

@@ -90,7 +90,7 @@ struct XT<2> {
 // per MFMA (measured +4-5% at cfg5; at T = 4 both were neutral to -12%).
 constexpr int kWideSched = 3;
 
-constexpr int kX3Waves = 4;  // waves per block: 32 samples each
+// kX3Waves (zf_flow_image.h): waves per block, 32 samples each
 static_assert(kX3Waves % 4 == 0, "whole 128-row NLL partial slots per block");
 
 // Tuning-only phase trace (a separate build with -DZF_X3_TRACE=1, never the
@@ -215,9 +215,9 @@ __device__ __forceinline__ void splitk(const floatx16& v, typename XT<NT>::E (&b
 }
 
 // f16x2: every swished layer (Dense_0 .. Dense_{n_hidden-1}) is packed with
-// its weights and bias multiplied by log2(e) (x3_pack), so its accumulator
-// holds v' = v*log2(e) and the sigmoid's exponent needs no multiply.
-constexpr float kSwishPrescale = 1.44269504088896341f;
+// its weights and bias multiplied by log2(e) (x3_pack; kSwishPrescale,
+// zf_flow_image.h), so its accumulator holds v' = v*log2(e) and the sigmoid's
+// exponent needs no multiply.
 
 // Layer-input activation: swish(v) (bf16x3), or f16x2's swish(v) * sc from
 // the prescaled v' with c = isc*log2(e) (isc = 1/sc a power of two):
