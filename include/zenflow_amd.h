@@ -640,6 +640,174 @@ int zf_trainer_get_opt_scalars(zf_trainer_t* trainer, int64_t* count, double* le
 int zf_trainer_set_opt_count(zf_trainer_t* trainer, int64_t count);
 
 /* ------------------------------------------------------------------------ */
+/* Conditioning networks — the `Phi` of examples/deep_set.ipynb: the network  */
+/* that produces the flow's condition and is trained together with the flow   */
+/* (cells `class NNBlock` / `class Phi` / `class DeepSetFlow` / `loss_fn_2`): */
+/*   BatchNorm -> (Dense, act) x depth -> Dense -> Dropout -> sum over sets   */
+/* The FLAX layers are restated (flax.linen.BatchNorm / Dense / Dropout, as   */
+/* the couplings' are), not called: no JAX is at hand.                        */
+/* ------------------------------------------------------------------------ */
+
+/* Segment sum over ragged sets — replaces `sum_matrix @ x` of Phi.__call__
+ * (the BCOO matrix that `preprocess` builds has one 1 per element row, in the
+ * row of its set; `off` is its CSR form: set s owns rows [off[s], off[s+1])).
+ *
+ *   out[s, f] = sum over i in [off[s], off[s+1]) of d(i, f),  0 <= f < F <= 64
+ *   d(i, f)   = h[i, f]                                  (rate == 0)
+ *             = keep(i, f) ? h[i, f] / (1 - rate) : 0    (0 < rate < 1, below)
+ *
+ * Offsets: S + 1 int64 on the device.  Before use they are clamped,
+ *   o[s] = max over j <= s of min(max(off[j], 0), rows),
+ * so any content of `off` addresses rows inside h only; host callers
+ * validate instead (zenflow_amd.nn).  Rows covered by no set are ignored;
+ * an empty set gives a row of +0.
+ *
+ * Order of the additions (fp32, no atomics).  It depends on the set's length
+ * n and on F alone — not on S, the grid, the set's place in the batch or its
+ * neighbours — so a set has the same bits wherever it stands:
+ *   - the set's rows are cut, from its first row, into chunks of
+ *     ZF_SEG_CHUNK rows (the last one shorter); one wave sums one chunk;
+ *   - with R = 64 / F (integer division) rows of a chunk per wave step, lane
+ *     (j, f), j < R, adds rows j, j + R, j + 2R, ... of the chunk in that
+ *     order, starting from +0;
+ *   - the chunk's sum of column f is ((p_0 + p_1) + p_2) + ... over the lane
+ *     partials p_j, j = 0 .. R - 1;
+ *   - the set's chunk sums, in chunk order, are a list of rows again and are
+ *     summed by the same three rules, level after level, until one is left.
+ * Long sets are thereby spread over many waves at every level: a batch with
+ * one set of 10^5 rows among sets of tens does not run as long as its longest
+ * set.
+ *
+ * set_index (rows int32, or NULL): receives set(i), the set that owns row i,
+ * or -1 for a row in no set — what zf_segment_bcast reads.
+ * workspace: zf_segment_workspace_bytes(rows, S, F) bytes on the device.
+ * ZF_EINVAL: NULL h / off / out / workspace, rows < 0, S < 0, F < 1, rate
+ * outside [0, 1); ZF_ENOTSUP: F > 64, S > 2^24, rows > 2^31 - 1.  Nothing is
+ * enqueued then. */
+#define ZF_SEG_CHUNK 512
+int64_t zf_segment_workspace_bytes(int64_t rows, int64_t sets, int F);
+int zf_segment_sum(const float* h, int64_t rows, int F, const int64_t* off, int64_t sets, float rate,
+                   uint64_t seed, float* out, int32_t* set_index, void* workspace, void* stream);
+
+/* Its reverse — the gradient of `sum_matrix @ Dropout(x)` with respect to x:
+ *   g_h[i, f] = gc[set(i), f] * keep(i, f) / (1 - rate),
+ * and 0 for rows in no set (set_index[i] outside [0, S): never dereferenced).
+ * rate == 0: a plain gather of gc rows.  Same error codes. */
+int zf_segment_bcast(const float* gc, const int32_t* set_index, int64_t rows, int F, int64_t sets, float rate,
+                     uint64_t seed, float* g_h, void* stream);
+
+/* Dropout — replaces nn.Dropout(rate, deterministic=not train) of Phi.__call__:
+ *   keep(i, f) = u01_co(philox_at(seed, i, f, ZF_DROPOUT_STREAM).v[ZF_DROPOUT_WORD]) >= rate
+ * with i the element row, f the column, Philox4x32-10 and u01_co (top 24
+ * bits / 2^24) as in zf_flow_sample; kept entries are divided by
+ * (float)1 - rate.  The mask is a function of (seed, i, f): the reverse pass
+ * recomputes it.  rate == 0 draws nothing.  jax.random's bits (the
+ * `rngs={"dropout": key}` stream) are not reproduced: parity is statistical. */
+#define ZF_DROPOUT_STREAM 0x64726f70u /* "drop" */
+#define ZF_DROPOUT_WORD 0
+
+#define ZF_POOL_NONE 0 /* one output row per input row (an NNBlock behind BatchNorm) */
+#define ZF_POOL_SUM 1  /* Phi: one output row per set */
+
+/* Replaces the configuration of Phi / NNBlock (out_dim, depth, width, act):
+ *   BatchNorm(use_running_average=not train)         when batch_norm
+ *   Dense(hidden[l]) + act, l = 0 .. n_hidden - 1
+ *   Dense(out_dim)
+ *   Dropout(dropout, deterministic=not train)
+ *   sum over each set's rows                          when pool == ZF_POOL_SUM
+ * Limits: 1 <= in_dim <= 64, 0 <= n_hidden <= 16, 1 <= hidden[l] <= 4096,
+ * 1 <= out_dim <= 64, 0 <= dropout < 1 (ZF_ENOTSUP beyond the sizes,
+ * ZF_EINVAL for the rest).  The offsets (in floats) into the natural blob are
+ * filled by zf_condnet_plan; every tensor starts at a multiple of 4 floats:
+ *   off_bn   -> BatchNorm_0 {mean[in_dim], var[in_dim], scale[in_dim], bias[in_dim]}
+ *               (-1 without batch_norm)
+ *   off_w[l] -> Dense_l.kernel, row-major (in_l, out_l); off_b[l] -> Dense_l.bias;
+ *               l = 0 .. n_hidden, the last layer has out = out_dim. */
+typedef struct zf_condnet_desc {
+  int32_t in_dim;
+  int32_t n_hidden;
+  int32_t hidden[16];
+  int32_t out_dim;
+  int32_t act;        /* ZF_ACT_* */
+  int32_t batch_norm; /* 0 / 1 */
+  int32_t pool;       /* ZF_POOL_* */
+  float dropout;
+  int32_t _pad;
+  int64_t off_bn;
+  int64_t off_w[17];
+  int64_t off_b[17];
+} zf_condnet_desc;
+
+typedef struct zf_condnet zf_condnet_t;
+
+/* Validate `desc` and fill its offsets; *blob_floats = size of the natural
+ * blob (padding between tensors included).  Host-side only. */
+int zf_condnet_plan(zf_condnet_desc* desc, int64_t* blob_floats);
+
+/* A handle owns a device copy of the blob (parameters and BatchNorm
+ * statistics), the activations of one pass of up to rows_max element rows in
+ * up to sets_max sets, the gradient and the optimiser state.  param_mask as
+ * zf_trainer_create's (1: parameter, 0: statistics or padding).  optim: the
+ * (n)adamw of zf_optim_desc, run as the chain scale_by_adam ->
+ * add_decayed_weights -> scale_by_learning_rate (NULL: optax.nadamw(1e-3),
+ * train.py:13-16).  What only a train-mode pass, its reverse and the
+ * optimiser read (pre-activations, gradients, the 128 MB split-K workspace) is
+ * allocated by the first call that needs it: a handle that only evaluates
+ * holds the blob and one activation per layer. */
+int zf_condnet_create(const zf_condnet_desc* desc, const float* blob_host, int64_t blob_floats,
+                      const unsigned char* param_mask, int64_t rows_max, int64_t sets_max,
+                      const zf_optim_desc* optim, zf_condnet_t** handle);
+int zf_condnet_destroy(zf_condnet_t* handle);
+
+/* Replaces Phi.__call__(x, sum_matrix, train) (and deep_set_flow.apply(...,
+ * train=True, mutable=["batch_stats"], rngs={"dropout": key}) for its phi
+ * half): x (rows, in_dim) on the device -> c_out, (sets, out_dim) with
+ * ZF_POOL_SUM (off: sets + 1 offsets on the device, as zf_segment_sum's) or
+ * (rows, out_dim) with ZF_POOL_NONE (off must be NULL; sets is ignored).
+ *   train != 0  BatchNorm on the statistics of all `rows` rows passed (padding
+ *               rows included: what nn.BatchNorm sees in the example), biased
+ *               variance, eps 1e-5, the rule of the couplings' BatchNorm
+ *               (bn_stats_kernel); update_stats != 0 also moves the running
+ *               statistics (0.99 old + 0.01 batch).  Dropout with `seed`.
+ *               Every activation the reverse pass reads is kept; the pass
+ *               stays pending for one zf_condnet_backward.
+ *   train == 0  the stored statistics, no dropout (`seed` is ignored);
+ *               update_stats must be 0; nothing stays pending.
+ * ZF_EINVAL (nothing enqueued): NULL x / c_out, rows outside [1, rows_max],
+ * sets outside [1, sets_max] or a NULL off with ZF_POOL_SUM, a non-NULL off
+ * with ZF_POOL_NONE, update_stats without train.  Every call drops a pending
+ * pass first. */
+int zf_condnet_forward(zf_condnet_t* handle, const float* x, int64_t rows, const int64_t* off, int64_t sets,
+                       int train, int update_stats, uint64_t seed, float* c_out, void* stream);
+
+/* Replaces jax.grad(loss_fn_2) for phi's parameters: gc (device, the shape of
+ * the pending forward's c_out) = d loss / d c, e.g. the gc of
+ * zf_trainer_step_cond_shard, of zf_trainer_sample_backward or of
+ * zf_trainer_log_prob_vjp.  grad_out (blob layout, fp32, device; may be NULL)
+ * receives d loss / d blob, zero on statistics and padding; the handle keeps
+ * a copy for zf_condnet_apply_gradient.  Weight and bias gradients are the
+ * trainer's fixed-order leaf trees (zf_reduce.h) over the element rows.
+ * d / d x is not formed.  One backward per train-mode forward: ZF_EINVAL "no
+ * forward pending" (nothing enqueued) otherwise — after an eval-mode
+ * forward too. */
+int zf_condnet_backward(zf_condnet_t* handle, const float* gc, float* grad_out, void* stream);
+
+/* Replaces opt.update + optax.apply_updates of `step`: the optimiser chain on
+ * grad (device, blob layout; NULL: the last backward's). */
+int zf_condnet_apply_gradient(zf_condnet_t* handle, const float* grad, void* stream);
+
+/* Replace the optimiser by a chain, as zf_trainer_set_optim_chain does (same
+ * stages, limits and messages).  Synchronises; resets moments and count. */
+int zf_condnet_set_optim_chain(zf_condnet_t* handle, const zf_optim_chain* chain,
+                               const unsigned char* decay_mask);
+
+/* Copy the blob (parameters + statistics) out / in.  These two synchronise
+ * with the host; no other zf_condnet_* or zf_segment_* entry does, and none
+ * captures a graph or communicates. */
+int zf_condnet_get_blob(zf_condnet_t* handle, float* blob_host);
+int zf_condnet_set_blob(zf_condnet_t* handle, const float* blob_host);
+
+/* ------------------------------------------------------------------------ */
 /* RCCL (over xGMI) — the NLL all-reduce of data-parallel log_prob and the  */
 /* trainer's all-gather.                                                      */
 /* ------------------------------------------------------------------------ */

@@ -9,10 +9,11 @@ modules holding a Flow build on.  All arithmetic runs in hand-written HIP kernel
 in include/zenflow_amd.h."""
 
 from .flow import BoundFlow, Flow
-from . import activations, bijectors, distributions, io, optim, utils
+from . import activations, bijectors, distributions, io, nn, optim, utils
 from .io import load_opt_state, load_variables, save_opt_state, save_variables
 from .module import Module, Variable
+from .nn import ConditionNet, ConditionTrainer
 from .random import PRNGKey
 from .train import Optimizer, adamw, nadamw, train
 
-__all__ = "Flow", "train", "BoundFlow", "PRNGKey", "save_variables", "load_variables", "save_opt_state", "load_opt_state", "optim", "nadamw", "adamw", "Optimizer", "Module", "Variable"
+__all__ = "Flow", "train", "BoundFlow", "PRNGKey", "save_variables", "load_variables", "save_opt_state", "load_opt_state", "optim", "nadamw", "adamw", "Optimizer", "Module", "Variable", "nn", "ConditionNet", "ConditionTrainer"

@@ -66,6 +66,11 @@ ZF_SCHED_PIECEWISE = 4
 ZF_SCHED_JOIN = 5
 ZF_SCHED_MAX_SEGMENTS = 4
 ZF_SCHED_PARAMS = 8
+ZF_SEG_CHUNK = 512
+ZF_DROPOUT_STREAM = 0x64726F70
+ZF_DROPOUT_WORD = 0
+ZF_POOL_NONE = 0
+ZF_POOL_SUM = 1
 
 
 class ZfOpDesc(C.Structure):
@@ -101,6 +106,23 @@ class ZfOptimStage(C.Structure):
 
 class ZfOptimChain(C.Structure):
     _fields_ = [("n_stages", C.c_int), ("_pad", C.c_int), ("stages", ZfOptimStage * ZF_OPT_MAX_STAGES)]
+
+
+class ZfCondnetDesc(C.Structure):
+    _fields_ = [
+        ("in_dim", C.c_int32),
+        ("n_hidden", C.c_int32),
+        ("hidden", C.c_int32 * 16),
+        ("out_dim", C.c_int32),
+        ("act", C.c_int32),
+        ("batch_norm", C.c_int32),
+        ("pool", C.c_int32),
+        ("dropout", C.c_float),
+        ("_pad", C.c_int32),
+        ("off_bn", C.c_int64),
+        ("off_w", C.c_int64 * 17),
+        ("off_b", C.c_int64 * 17),
+    ]
 
 
 # zf_allgather_fn(ctx, send, recv, bytes, stream) and zf_comm_desc
@@ -194,6 +216,18 @@ SIGNATURES = {
     "zf_trainer_set_opt_slot": (_int, [_vp, _int, _vp]),
     "zf_trainer_get_opt_scalars": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "zf_trainer_set_opt_count": (_int, [_vp, _i64]),
+    "zf_segment_workspace_bytes": (_i64, [_i64, _i64, _int]),
+    "zf_segment_sum": (_int, [_vp, _i64, _int, _vp, _i64, C.c_float, _u64, _vp, _vp, _vp, _vp]),
+    "zf_segment_bcast": (_int, [_vp, _vp, _i64, _int, _i64, C.c_float, _u64, _vp, _vp]),
+    "zf_condnet_plan": (_int, [C.POINTER(ZfCondnetDesc), C.POINTER(_i64)]),
+    "zf_condnet_create": (_int, [C.POINTER(ZfCondnetDesc), _vp, _i64, _vp, _i64, _i64, _vp, C.POINTER(_vp)]),
+    "zf_condnet_destroy": (_int, [_vp]),
+    "zf_condnet_forward": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _u64, _vp, _vp]),
+    "zf_condnet_backward": (_int, [_vp, _vp, _vp, _vp]),
+    "zf_condnet_apply_gradient": (_int, [_vp, _vp, _vp]),
+    "zf_condnet_set_optim_chain": (_int, [_vp, _vp, _vp]),
+    "zf_condnet_get_blob": (_int, [_vp, _vp]),
+    "zf_condnet_set_blob": (_int, [_vp, _vp]),
     "zf_latent_sample": (_int, [_int, _dbl, _u64, _vp, _i64, _int, _vp]),
     "zf_flow_set_bn_stats": (_int, [_vp, _int, _vp, _vp]),
     "zf_flow_set_sb_stats": (_int, [_vp, _int, _vp, _vp]),

@@ -30,6 +30,23 @@ constexpr int kFormSgd = 1;      // [clip_by_global_norm] [trace] scale_by_learn
 constexpr int kFormAdam = 2;     // [clip_by_global_norm] scale_by_adam [add_decayed_weights] scale_by_learning_rate
 constexpr int kFormLion = 3;     // [clip_by_global_norm] scale_by_lion [add_decayed_weights] scale_by_learning_rate
 
+// A validated zf_optim_chain as its owner (the trainer, a conditioning
+// network) holds it: the stage list without its moment arrays, the form, and
+// what the prologue needs.
+struct ChainPlan {
+  ChainArgs args{};
+  int form = kFormGeneric;
+  int n_slots = 0;
+  bool clip = false, has_lr = false, has_adam = false, masked = false;
+  float max_norm = 0.f, b1 = 0.f, b2 = 0.f;
+  zf_schedule sched{};
+};
+
+// Validate `chain` (ZF_EINVAL / ZF_ENOTSUP, the message names the stage) and
+// lower it to `out`.  has_decay_mask: the caller has a mask for a masked
+// add_decayed_weights.  Host-side only.
+int optim_plan_chain(const zf_optim_chain* chain, bool has_decay_mask, ChainPlan* out);
+
 // One step of the chain on stream st: [sum of squares] -> prologue -> update.
 // prm / g / mask: the blob, its gradient and the parameter mask (n entries);
 // dmask: the decay mask or NULL; leaf: ceil(n / kNormSpan) doubles.

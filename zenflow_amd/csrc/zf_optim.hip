@@ -264,4 +264,122 @@ int optim_set_count(float* bc, int count, float b1, float b2) {
   return ZF_OK;
 }
 
+// ---- chain validation (host) ------------------------------------------------
+namespace {
+
+// enotsup with a formatted message
+int enotsupf(const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return enotsup(buf);
+}
+
+const char* stage_name(int kind) {
+  switch (kind) {
+    case ZF_OPT_CLIP_BY_GLOBAL_NORM: return "clip_by_global_norm";
+    case ZF_OPT_CLIP: return "clip";
+    case ZF_OPT_SCALE_BY_ADAM: return "scale_by_adam";
+    case ZF_OPT_SCALE_BY_LION: return "scale_by_lion";
+    case ZF_OPT_TRACE: return "trace";
+    case ZF_OPT_ADD_DECAYED_WEIGHTS: return "add_decayed_weights";
+    case ZF_OPT_SCALE: return "scale";
+    case ZF_OPT_SCALE_BY_LEARNING_RATE: return "scale_by_learning_rate";
+    default: return nullptr;
+  }
+}
+
+int stage_slots(int kind) {
+  return kind == ZF_OPT_SCALE_BY_ADAM ? 2 : (kind == ZF_OPT_SCALE_BY_LION || kind == ZF_OPT_TRACE) ? 1 : 0;
+}
+
+int check_schedule(const zf_schedule& s) {
+  if (s.n_segments < 1 || s.n_segments > ZF_SCHED_MAX_SEGMENTS)
+    return enotsupf("optimiser chain: a schedule of %d joined segments (at most %d)", s.n_segments,
+                   ZF_SCHED_MAX_SEGMENTS);
+  for (int k = 0; k < s.n_segments; ++k) {
+    if (s.seg_kind[k] < ZF_SCHED_CONSTANT || s.seg_kind[k] > ZF_SCHED_PIECEWISE)
+      return einval("optimiser chain: schedule segment %d has unknown kind %d", k, s.seg_kind[k]);
+    if (s.seg_kind[k] == ZF_SCHED_PIECEWISE && (s.p[k][1] < 0 || s.p[k][1] > 3))
+      return enotsupf("optimiser chain: piecewise_constant_schedule with more than 3 boundaries");
+    if (s.seg_kind[k] == ZF_SCHED_COSINE && !(s.p[k][1] > 0))
+      return einval("optimiser chain: cosine_decay_schedule needs decay_steps > 0");
+    if (s.seg_kind[k] == ZF_SCHED_EXPONENTIAL && !(s.p[k][1] > 0))
+      return einval("optimiser chain: exponential_decay needs transition_steps > 0");
+  }
+  return ZF_OK;
+}
+
+}  // namespace
+
+int optim_plan_chain(const zf_optim_chain* chain, bool has_decay_mask, ChainPlan* out) {
+  const int S = chain->n_stages;
+  if (S < 1) return einval("optimiser chain: no stage");
+  if (S > ZF_OPT_MAX_STAGES) return enotsupf("optimiser chain: %d stages (at most %d)", S, ZF_OPT_MAX_STAGES);
+  ChainArgs a{};
+  a.n = S;
+  int slots = 0, n_clip = 0, n_adam = 0, n_lr = 0, lr_at = -1, adam_at = -1;
+  bool masked = false;
+  for (int k = 0; k < S; ++k) {
+    const zf_optim_stage& s = chain->stages[k];
+    const char* name = stage_name(s.kind);
+    if (!name) return einval("optimiser chain: stage %d has unknown kind %d", k, s.kind);
+    if (s.kind == ZF_OPT_CLIP_BY_GLOBAL_NORM) {
+      if (++n_clip > 1) return enotsupf("optimiser chain: stage %d: more than one clip_by_global_norm", k);
+      if (k != 0)
+        return enotsupf("optimiser chain: stage %d: clip_by_global_norm after %s (it must come before every "
+                        "stage that changes the update: the norm is the raw gradient's)", k,
+                        stage_name(chain->stages[k - 1].kind));
+    }
+    if (s.kind == ZF_OPT_SCALE_BY_ADAM && ++n_adam > 1)
+      return enotsupf("optimiser chain: stage %d: more than one scale_by_adam", k);
+    if (s.kind == ZF_OPT_SCALE_BY_LEARNING_RATE) {
+      if (++n_lr > 1) return enotsupf("optimiser chain: stage %d: more than one scale_by_learning_rate", k);
+      const int rc = check_schedule(s.sched);
+      if (rc) return rc;
+      lr_at = k;
+    }
+    if (s.kind == ZF_OPT_SCALE_BY_ADAM) adam_at = k;
+    if (s.kind == ZF_OPT_ADD_DECAYED_WEIGHTS && (s.flags & ZF_OPT_FLAG_MASKED)) {
+      if (!has_decay_mask)
+        return einval("optimiser chain: stage %d: add_decayed_weights is masked but decay_mask is NULL", k);
+      masked = true;
+    }
+    a.st[k].kind = s.kind;
+    a.st[k].flags = s.flags;
+    a.st[k].slot = slots;
+    for (int j = 0; j < 4; ++j) a.st[k].p[j] = s.p[j];
+    slots += stage_slots(s.kind);
+    if (slots > ZF_OPT_MAX_SLOTS)
+      return enotsupf("optimiser chain: stage %d (%s) needs moment array %d (at most %d)", k, name, slots,
+                      ZF_OPT_MAX_SLOTS);
+  }
+  // the forms the aliases build: [clip] body [decay] lr
+  const int first = n_clip;
+  auto kind = [&](int k) { return k < S ? chain->stages[k].kind : 0; };
+  int form = kFormGeneric;
+  if (kind(S - 1) == ZF_OPT_SCALE_BY_LEARNING_RATE) {
+    if (S == first + 1 || (S == first + 2 && kind(first) == ZF_OPT_TRACE)) form = kFormSgd;
+    const bool body_decay = S == first + 3 && kind(first + 1) == ZF_OPT_ADD_DECAYED_WEIGHTS;
+    if ((S == first + 2 || body_decay) && kind(first) == ZF_OPT_SCALE_BY_ADAM) form = kFormAdam;
+    if ((S == first + 2 || body_decay) && kind(first) == ZF_OPT_SCALE_BY_LION) form = kFormLion;
+  }
+  ChainPlan p;
+  p.args = a;
+  p.form = form;
+  p.n_slots = slots;
+  p.clip = n_clip > 0;
+  p.max_norm = n_clip ? chain->stages[0].p[0] : 0.f;
+  p.has_lr = lr_at >= 0;
+  if (lr_at >= 0) p.sched = chain->stages[lr_at].sched;
+  p.has_adam = adam_at >= 0;
+  p.b1 = adam_at >= 0 ? chain->stages[adam_at].p[0] : 0.f;
+  p.b2 = adam_at >= 0 ? chain->stages[adam_at].p[1] : 0.f;
+  p.masked = masked;
+  *out = p;
+  return ZF_OK;
+}
+
 }  // namespace zf

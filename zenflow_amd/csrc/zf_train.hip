@@ -1244,51 +1244,6 @@ int zf_trainer_set_blob(zf_trainer_t* t, const float* blob_host) {
 namespace zf {
 namespace {
 
-// enotsup with a formatted message
-int enotsupf(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return enotsup(buf);
-}
-
-const char* stage_name(int kind) {
-  switch (kind) {
-    case ZF_OPT_CLIP_BY_GLOBAL_NORM: return "clip_by_global_norm";
-    case ZF_OPT_CLIP: return "clip";
-    case ZF_OPT_SCALE_BY_ADAM: return "scale_by_adam";
-    case ZF_OPT_SCALE_BY_LION: return "scale_by_lion";
-    case ZF_OPT_TRACE: return "trace";
-    case ZF_OPT_ADD_DECAYED_WEIGHTS: return "add_decayed_weights";
-    case ZF_OPT_SCALE: return "scale";
-    case ZF_OPT_SCALE_BY_LEARNING_RATE: return "scale_by_learning_rate";
-    default: return nullptr;
-  }
-}
-
-int stage_slots(int kind) {
-  return kind == ZF_OPT_SCALE_BY_ADAM ? 2 : (kind == ZF_OPT_SCALE_BY_LION || kind == ZF_OPT_TRACE) ? 1 : 0;
-}
-
-int check_schedule(const zf_schedule& s) {
-  if (s.n_segments < 1 || s.n_segments > ZF_SCHED_MAX_SEGMENTS)
-    return enotsupf("optimiser chain: a schedule of %d joined segments (at most %d)", s.n_segments,
-                   ZF_SCHED_MAX_SEGMENTS);
-  for (int k = 0; k < s.n_segments; ++k) {
-    if (s.seg_kind[k] < ZF_SCHED_CONSTANT || s.seg_kind[k] > ZF_SCHED_PIECEWISE)
-      return einval("optimiser chain: schedule segment %d has unknown kind %d", k, s.seg_kind[k]);
-    if (s.seg_kind[k] == ZF_SCHED_PIECEWISE && (s.p[k][1] < 0 || s.p[k][1] > 3))
-      return enotsupf("optimiser chain: piecewise_constant_schedule with more than 3 boundaries");
-    if (s.seg_kind[k] == ZF_SCHED_COSINE && !(s.p[k][1] > 0))
-      return einval("optimiser chain: cosine_decay_schedule needs decay_steps > 0");
-    if (s.seg_kind[k] == ZF_SCHED_EXPONENTIAL && !(s.p[k][1] > 0))
-      return einval("optimiser chain: exponential_decay needs transition_steps > 0");
-  }
-  return ZF_OK;
-}
-
 void free_chain(zf_trainer_t* t) {
   for (void* p : t->opt_bufs) (void)hipFree(p);
   t->opt_bufs.clear();
@@ -1315,66 +1270,20 @@ extern "C" {
 int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, const unsigned char* decay_mask) {
   if (!t || !chain) return zf::einval("NULL argument");
   zf::set_pending(t, zf::kPendNone);
-  const int S = chain->n_stages;
-  if (S < 1) return zf::einval("optimiser chain: no stage");
-  if (S > ZF_OPT_MAX_STAGES)
-    return zf::enotsupf("optimiser chain: %d stages (at most %d)", S, ZF_OPT_MAX_STAGES);
-  zf::ChainArgs a{};
-  a.n = S;
-  int slots = 0, n_clip = 0, n_adam = 0, n_lr = 0, lr_at = -1, adam_at = -1;
-  bool masked = false;
-  for (int k = 0; k < S; ++k) {
-    const zf_optim_stage& s = chain->stages[k];
-    const char* name = zf::stage_name(s.kind);
-    if (!name) return zf::einval("optimiser chain: stage %d has unknown kind %d", k, s.kind);
-    if (s.kind == ZF_OPT_CLIP_BY_GLOBAL_NORM) {
-      if (++n_clip > 1) return zf::enotsupf("optimiser chain: stage %d: more than one clip_by_global_norm", k);
-      if (k != 0)
-        return zf::enotsupf("optimiser chain: stage %d: clip_by_global_norm after %s (it must come before every "
-                           "stage that changes the update: the norm is the raw gradient's)", k,
-                           zf::stage_name(chain->stages[k - 1].kind));
-    }
-    if (s.kind == ZF_OPT_SCALE_BY_ADAM && ++n_adam > 1)
-      return zf::enotsupf("optimiser chain: stage %d: more than one scale_by_adam", k);
-    if (s.kind == ZF_OPT_SCALE_BY_LEARNING_RATE) {
-      if (++n_lr > 1) return zf::enotsupf("optimiser chain: stage %d: more than one scale_by_learning_rate", k);
-      const int rc = zf::check_schedule(s.sched);
-      if (rc) return rc;
-      lr_at = k;
-    }
-    if (s.kind == ZF_OPT_SCALE_BY_ADAM) adam_at = k;
-    if (s.kind == ZF_OPT_ADD_DECAYED_WEIGHTS && (s.flags & ZF_OPT_FLAG_MASKED)) {
-      if (!decay_mask) return zf::einval("optimiser chain: stage %d: add_decayed_weights is masked but decay_mask is NULL", k);
-      masked = true;
-    }
-    a.st[k].kind = s.kind;
-    a.st[k].flags = s.flags;
-    a.st[k].slot = slots;
-    for (int j = 0; j < 4; ++j) a.st[k].p[j] = s.p[j];
-    slots += zf::stage_slots(s.kind);
-    if (slots > ZF_OPT_MAX_SLOTS)
-      return zf::enotsupf("optimiser chain: stage %d (%s) needs moment array %d (at most %d)", k, name, slots,
-                         ZF_OPT_MAX_SLOTS);
-  }
-  // the forms the aliases build: [clip] body [decay] lr
-  const int first = n_clip;
-  auto kind = [&](int k) { return k < S ? chain->stages[k].kind : 0; };
-  int form = zf::kFormGeneric;
-  if (kind(S - 1) == ZF_OPT_SCALE_BY_LEARNING_RATE) {
-    if (S == first + 1 || (S == first + 2 && kind(first) == ZF_OPT_TRACE)) form = zf::kFormSgd;
-    const bool body_decay = S == first + 3 && kind(first + 1) == ZF_OPT_ADD_DECAYED_WEIGHTS;
-    if ((S == first + 2 || body_decay) && kind(first) == ZF_OPT_SCALE_BY_ADAM) form = zf::kFormAdam;
-    if ((S == first + 2 || body_decay) && kind(first) == ZF_OPT_SCALE_BY_LION) form = zf::kFormLion;
-  }
+  // the stage list, its form and what the prologue needs (zf_optim.hip)
+  zf::ChainPlan plan;
+  int rc = zf::optim_plan_chain(chain, decay_mask != nullptr, &plan);
+  if (rc) return rc;
+  zf::ChainArgs a = plan.args;
+  const int slots = plan.n_slots;
   ZF_TRY_HIP(hipStreamSynchronize(t->cap));
   ZF_TRY_HIP(hipDeviceSynchronize());
   zf::drop_graphs(t->graphs);
   zf::drop_graphs(t->graphs_w);
   zf::free_chain(t);
   const size_t need = (size_t)t->nat_floats;
-  int rc = ZF_OK;
   for (int k = 0; k < slots && !rc; ++k) rc = zf::opt_alloc(t, (void**)&a.slot[k], need * sizeof(float));
-  if (!rc && masked) {
+  if (!rc && plan.masked) {
     rc = zf::opt_alloc(t, (void**)&t->d_dmask, need);
     if (!rc) {
       const hipError_t e = hipMemcpy(t->d_dmask, decay_mask, need, hipMemcpyHostToDevice);
@@ -1389,15 +1298,15 @@ int zf_trainer_set_optim_chain(zf_trainer_t* t, const zf_optim_chain* chain, con
     return rc;
   }
   t->cargs = a;
-  t->chain_form = form;
+  t->chain_form = plan.form;
   t->n_slots = slots;
-  t->chain_clip = n_clip > 0;
-  t->max_norm = n_clip ? chain->stages[0].p[0] : 0.f;
-  t->chain_lr = lr_at >= 0;
-  if (lr_at >= 0) t->sched = chain->stages[lr_at].sched;
-  t->chain_adam = adam_at >= 0;
-  t->chain_b1 = adam_at >= 0 ? chain->stages[adam_at].p[0] : 0.f;
-  t->chain_b2 = adam_at >= 0 ? chain->stages[adam_at].p[1] : 0.f;
+  t->chain_clip = plan.clip;
+  t->max_norm = plan.max_norm;
+  t->chain_lr = plan.has_lr;
+  if (plan.has_lr) t->sched = plan.sched;
+  t->chain_adam = plan.has_adam;
+  t->chain_b1 = plan.b1;
+  t->chain_b2 = plan.b2;
   t->t = 0;
   t->chain_on = true;
   return ZF_OK;
