@@ -696,6 +696,25 @@ int zf_segment_sum(const float* h, int64_t rows, int F, const int64_t* off, int6
 int zf_segment_bcast(const float* gc, const int32_t* set_index, int64_t rows, int F, int64_t sets, float rate,
                      uint64_t seed, float* g_h, void* stream);
 
+/* Repeat over ragged sets — replaces `jnp.repeat(c, sizes, axis=0)` of
+ * DeepSetFlow.sample, with the sizes in CSR form (off[s + 1] - off[s] copies
+ * of row s):
+ *   out[i, :] = c[set(i), :]  for every row i < rows,  0 < F <= 64,
+ * and +0 for a row in no set (before the first offset, from the last one on,
+ * padding).  c: (sets, F) on the device; off: sets + 1 int64 on the device,
+ * clamped before use by the rule of zf_segment_sum, so any content of `off`
+ * reads inside c and writes inside out only; out: (rows, F).
+ * set_index (rows int32, or NULL) receives set(i) or -1, exactly as
+ * zf_segment_sum writes it.  workspace: zf_segment_workspace_bytes(rows,
+ * sets, F) bytes.  One search over the clamped offsets per row: the time does
+ * not depend on how the rows are divided into sets.  No atomics: a copy, the
+ * same bits every time.  Its reverse (the gradient with respect to c) is
+ * zf_segment_sum of the rows' gradients with rate 0 over the same offsets.
+ * Limits and error codes are zf_segment_sum's (there is no rate), returned
+ * before anything is enqueued. */
+int zf_segment_repeat(const float* c, int64_t sets, int F, const int64_t* off, int64_t rows, float* out,
+                      int32_t* set_index, void* workspace, void* stream);
+
 /* Dropout — replaces nn.Dropout(rate, deterministic=not train) of Phi.__call__:
  *   keep(i, f) = u01_co(philox_at(seed, i, f, ZF_DROPOUT_STREAM).v[ZF_DROPOUT_WORD]) >= rate
  * with i the element row, f the column, Philox4x32-10 and u01_co (top 24
@@ -787,10 +806,31 @@ int zf_condnet_forward(zf_condnet_t* handle, const float* x, int64_t rows, const
  * receives d loss / d blob, zero on statistics and padding; the handle keeps
  * a copy for zf_condnet_apply_gradient.  Weight and bias gradients are the
  * trainer's fixed-order leaf trees (zf_reduce.h) over the element rows.
- * d / d x is not formed.  One backward per train-mode forward: ZF_EINVAL "no
+ * d / d x is not formed here (zf_condnet_backward_input forms it).  One
+ * reverse per train-mode forward, through either entry: ZF_EINVAL "no
  * forward pending" (nothing enqueued) otherwise — after an eval-mode
  * forward too. */
 int zf_condnet_backward(zf_condnet_t* handle, const float* gc, float* grad_out, void* stream);
+
+/* Replaces jax.grad(loss_fn) of the notebook's first half (`class DeepSet`:
+ * rho(phi(x))) for the network's input as well: zf_condnet_backward plus
+ * gx_out (device, (rows of the pending pass, in_dim) fp32, not NULL), which
+ * receives d loss / d x — what sends a loss behind this network on into the
+ * network in front of it (rho's gx is phi's gc).  grad_out and the kept
+ * gradient have the bits zf_condnet_backward gives for the same pass.
+ *   without BatchNorm  the first Dense layer's input-gradient GEMM,
+ *                      gx = g_0 . W_0^T, written to gx_out;
+ *   with BatchNorm     the train-mode reverse with the batch terms,
+ *                      gx = rstd * (gUhat - mean(gUhat) - u_hat * mean(gUhat * u_hat)),
+ *                      gUhat = gUbn * scale, the means over all rows passed
+ *                      (padding rows are in the forward's statistics); the
+ *                      two column sums are the ones the scale and bias
+ *                      gradients reduce, formed once.
+ * No atomics: the same pass gives the same gx bits.  The pending rules are
+ * zf_condnet_backward's; a NULL gx_out is ZF_EINVAL with nothing enqueued and
+ * the pass still pending.  An eval-mode forward leaves nothing pending: there
+ * is no eval-mode input gradient. */
+int zf_condnet_backward_input(zf_condnet_t* handle, const float* gc, float* grad_out, float* gx_out, void* stream);
 
 /* Replaces opt.update + optax.apply_updates of `step`: the optimiser chain on
  * grad (device, blob layout; NULL: the last backward's). */

@@ -219,6 +219,8 @@ SIGNATURES = {
     "zf_segment_workspace_bytes": (_i64, [_i64, _i64, _int]),
     "zf_segment_sum": (_int, [_vp, _i64, _int, _vp, _i64, C.c_float, _u64, _vp, _vp, _vp, _vp]),
     "zf_segment_bcast": (_int, [_vp, _vp, _i64, _int, _i64, C.c_float, _u64, _vp, _vp]),
+    "zf_segment_repeat": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "zf_condnet_backward_input": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "zf_condnet_plan": (_int, [C.POINTER(ZfCondnetDesc), C.POINTER(_i64)]),
     "zf_condnet_create": (_int, [C.POINTER(ZfCondnetDesc), _vp, _i64, _vp, _i64, _i64, _vp, C.POINTER(_vp)]),
     "zf_condnet_destroy": (_int, [_vp]),

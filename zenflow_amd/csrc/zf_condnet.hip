@@ -1,15 +1,15 @@
 // Conditioning networks on the device: the `Phi` of examples/deep_set.ipynb
 // (cells `class NNBlock` / `class Phi` / `class DeepSetFlow` / `loss_fn_2`),
 //   BatchNorm -> (Dense, act) x depth -> Dense -> Dropout -> sum over each set,
-// forward, reverse (parameter gradients for a given d loss / d c) and the
+// forward, reverse (parameter and input gradients for a given d loss / d c) and the
 // optimiser update, behind zf_condnet_* (include/zenflow_amd.h); and the
-// standalone segment sum / broadcast, zf_segment_*.
+// standalone segment sum / broadcast / repeat, zf_segment_*.
 //
 // The Dense layers, the weight-gradient trees, BatchNorm and the optimiser
 // are the trainer's, included as they are (zf_gemm.h, zf_reduce.h,
 // zf_train_kernels.h, zf_optim.h): this unit instantiates its own copies of
 // those kernels, the trainer's code object is untouched.  New here: the
-// segmented reduction over ragged sets, its reverse, and dropout.
+// segmented reduction over ragged sets, its reverse, the repeat, and dropout.
 #include "zf_gemm.h"
 #include "zf_internal.h"
 #include "zf_optim.h"
@@ -178,6 +178,40 @@ __global__ void seg_bcast_kernel(const float* __restrict__ gc, const int* __rest
   g[t] = drop_apply<DROP>(v, seed, i, f, rate, keep_prob);
 }
 
+// ---- the repeat: out[i, :] = c[set(i), :] from the clamped offsets ------------------
+// One block per kRepRows consecutive rows.  Thread r finds the set of the
+// block's row r by bisection over o[0 .. S] (the last s with o[s] <= i; a row
+// before o[0] or from o[S] on is in no set: -1), leaves it in LDS and, with
+// set_index, in memory; the block then writes its kRepRows * F floats in
+// element order.  The work of a row does not depend on its set's length.
+constexpr int kRepRows = 256;
+__global__ __launch_bounds__(kRepRows) void seg_repeat_kernel(const float* __restrict__ c, int F, long long S,
+                                                              const long long* __restrict__ o, long long rows,
+                                                              float* __restrict__ out, int* __restrict__ set_index) {
+  __shared__ int sidx[kRepRows];
+  const int t = threadIdx.x;
+  const long long r0 = (long long)blockIdx.x * kRepRows, i = r0 + t;
+  int s = -1;
+  if (i < rows && i >= o[0] && i < o[S]) {
+    long long lo = 0, hi = S;  // o[lo] <= i < o[hi]
+    while (hi - lo > 1) {
+      const long long mid = lo + (hi - lo) / 2;
+      if (o[mid] <= i) lo = mid;
+      else hi = mid;
+    }
+    s = (int)lo;
+  }
+  sidx[t] = s;
+  if (set_index && i < rows) set_index[i] = s;
+  __syncthreads();
+  const int n = (int)min((long long)kRepRows, rows - r0) * F;
+  for (int e = t; e < n; e += kRepRows) {
+    const int r = e / F, f = e - r * F;
+    const int q = sidx[r];
+    out[r0 * F + e] = q >= 0 ? c[(long long)q * F + f] : 0.f;
+  }
+}
+
 // The levels of one segment sum: level 0 sums the chunks of h's rows, level
 // k > 0 those of level k - 1's chunk sums (a set's chunk sums are consecutive
 // rows of `part`, its offsets the chunk counts cb: again sets of rows), until
@@ -256,6 +290,24 @@ int seg_bcast_launch(const float* gc, const int* idx, long long rows, int F, lon
     hipLaunchKernelGGL(seg_bcast_kernel<false>, dim3(blocks_for(rows * F)), dim3(256), 0, st, gc, idx, rows, F, S,
                        rate, kp, seed, g);
   ZF_CHECK_LAUNCH("seg_bcast_kernel");
+  return ZF_OK;
+}
+
+// The plan kernel for the clamped offsets (the workspace's first level: o, cb), then the repeat.
+int seg_repeat_launch(const float* c, long long S, int F, const long long* off, long long rows, float* out,
+                      int* set_index, void* ws, hipStream_t st) {
+  if (rows == 0) return ZF_OK;
+  if (S == 0) {  // no set: every row is in none
+    ZF_TRY_HIP(hipMemsetAsync(out, 0, (size_t)rows * F * sizeof(float), st));
+    if (set_index) ZF_TRY_HIP(hipMemsetAsync(set_index, 0xff, (size_t)rows * sizeof(int), st));
+    return ZF_OK;
+  }
+  long long* o = (long long*)ws;
+  hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(kPlanThreads), 0, st, off, S, rows, 0ll, o, o + (S + 1));
+  ZF_CHECK_LAUNCH("seg_plan_kernel");
+  hipLaunchKernelGGL(seg_repeat_kernel, dim3((unsigned)((rows + kRepRows - 1) / kRepRows)), dim3(kRepRows), 0, st, c,
+                     F, S, (const long long*)o, rows, out, set_index);
+  ZF_CHECK_LAUNCH("seg_repeat_kernel");
   return ZF_OK;
 }
 
@@ -486,8 +538,11 @@ int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long 
 // The reverse pass: gc -> the gradient of the last Dense's output (through the
 // pooling and dropout), the Dense chain last layer first (weight and bias
 // gradients queued into the fp64 accumulator, input gradients through the
-// activation), BatchNorm's scale and bias, then the cast to fp32.
-int cn_backward(zf_condnet* h, const float* gc, float* grad_out, hipStream_t st) {
+// activation), BatchNorm's scale and bias, then the cast to fp32.  With gx_out
+// the chain goes on to the network's input: the first layer's input-gradient
+// GEMM (without BatchNorm, straight into gx_out) or BatchNorm's train-mode
+// reverse on the column sums the scale and bias gradients reduce anyway.
+int cn_backward(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, hipStream_t st) {
   const int B = (int)h->pend_rows;
   const bool pool = h->desc.pool == ZF_POOL_SUM;
   const float rate = h->desc.dropout;
@@ -512,8 +567,8 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, hipStream_t st)
     rc = wgrad_deferred(wq, in_w, out_w, B, leaves_for(B, B, 1, cap), hin, gout, h->d_g64 + h->desc.off_w[l],
                         h->d_g64 + h->desc.off_b[l], h->d_ws, h->d_ws2, st);
     if (rc) return rc;
-    if (l == 0 && !h->desc.batch_norm) break;  // d / d x is not formed
-    float* const gin = l == 0 ? h->d_gu : (which ? h->d_gb : h->d_ga);
+    if (l == 0 && !h->desc.batch_norm && !gx_out) break;  // d / d x is not asked for
+    float* const gin = l == 0 ? (h->desc.batch_norm ? h->d_gu : gx_out) : (which ? h->d_gb : h->d_ga);
     if ((rc = wgrad_before_write(wq, gin, st))) return rc;  // a deferred dW GEMM still reads it
     rc = gemm(true, B, B, in_w, out_w, gout, out_w, h->d_nat + h->desc.off_w[l], out_w, gin, in_w, st,
               l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? h->Z[l - 1] : nullptr, h->desc.act, h->d_split,
@@ -524,7 +579,7 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, hipStream_t st)
   }
   if ((rc = wgrad_flush(wq, st))) return rc;
   if (h->desc.batch_norm) {
-    // scale / bias: the sums of gUbn * Uhat and gUbn over the rows (x is data: no batch term)
+    // scale / bias: the sums of gUbn * Uhat and gUbn over the rows
     const int DC = h->in;
     const Leaves lbn = leaves_for(B, B, 1, kBnLeafCap);
     double* gbn = h->d_g64 + h->desc.off_bn;
@@ -534,6 +589,14 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, hipStream_t st)
     if ((rc = launch_tree_cols(h->d_leaf, lbn.n, 2 * DC, h->d_roots, st, h->d_leaf2))) return rc;
     ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, h->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
     ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, h->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (gx_out) {
+      // d / d x: the batch terms are those two sums over all B rows of the pass (padding rows are in the statistics)
+      hipLaunchKernelGGL(bn_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)h->d_gu,
+                         (const float*)h->d_uhat, (const float*)(h->d_nat + h->desc.off_bn + 2 * DC),
+                         (const float*)h->d_rstd, (const double*)h->d_roots, (const double*)(h->d_roots + DC), gx_out,
+                         B, (long long)B, DC);
+      ZF_CHECK_LAUNCH("bn_bwd_kernel");
+    }
   }
   hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(h->nat_floats)), dim3(256), 0, st,
                      (const double*)h->d_g64, (long long)h->nat_floats, h->d_grad, (float*)nullptr, 0.f, 0.f);
@@ -542,6 +605,16 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, hipStream_t st)
   if (grad_out && grad_out != h->d_grad)
     ZF_TRY_HIP(hipMemcpyAsync(grad_out, h->d_grad, (size_t)h->nat_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
   return ZF_OK;
+}
+
+// Both reverse entries: zf_condnet_backward is the view without gx_out.
+int cn_backward_entry(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, bool want_gx, void* stream) {
+  if (!h) return einval("condnet is NULL");
+  if (!h->pending) return einval("no forward pending");
+  if (!gc) return einval("gc is NULL");
+  if (want_gx && !gx_out) return einval("gx_out is NULL");  // the pass stays pending
+  h->pending = false;  // one backward per forward
+  return cn_backward(h, gc, grad_out, gx_out, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -568,6 +641,15 @@ int zf_segment_bcast(const float* gc, const int32_t* set_index, int64_t rows, in
   const int rc = zf::seg_check(gc, set_index, g_h, rows, F, sets, rate);
   if (rc) return rc;
   return zf::seg_bcast_launch(gc, set_index, rows, F, sets, rate, seed, g_h, (hipStream_t)stream);
+}
+
+int zf_segment_repeat(const float* c, int64_t sets, int F, const int64_t* off, int64_t rows, float* out,
+                      int32_t* set_index, void* workspace, void* stream) {
+  const int rc = zf::seg_check(c, off, out, rows, F, sets, 0.f);
+  if (rc) return rc;
+  if (!workspace) return zf::einval("segment: NULL workspace");
+  return zf::seg_repeat_launch(c, sets, F, (const long long*)off, rows, out, set_index, workspace,
+                               (hipStream_t)stream);
 }
 
 int zf_condnet_plan(zf_condnet_desc* d, int64_t* blob_floats) {
@@ -698,11 +780,11 @@ int zf_condnet_forward(zf_condnet_t* h, const float* x, int64_t rows, const int6
 }
 
 int zf_condnet_backward(zf_condnet_t* h, const float* gc, float* grad_out, void* stream) {
-  if (!h) return zf::einval("condnet is NULL");
-  if (!h->pending) return zf::einval("no forward pending");
-  if (!gc) return zf::einval("gc is NULL");
-  h->pending = false;  // one backward per forward
-  return zf::cn_backward(h, gc, grad_out, (hipStream_t)stream);
+  return zf::cn_backward_entry(h, gc, grad_out, nullptr, false, stream);
+}
+
+int zf_condnet_backward_input(zf_condnet_t* h, const float* gc, float* grad_out, float* gx_out, void* stream) {
+  return zf::cn_backward_entry(h, gc, grad_out, gx_out, true, stream);
 }
 
 int zf_condnet_apply_gradient(zf_condnet_t* h, const float* grad, void* stream) {

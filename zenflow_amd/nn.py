@@ -19,6 +19,19 @@ with nothing leaving the device.  The sets are given in CSR form: ``offsets``
 (S + 1 non-decreasing integers, set s owns the rows ``offsets[s]:offsets[s+1]``)
 instead of the notebook's ``sum_matrix``.
 
+The notebook's first half (``class DeepSet`` / ``loss_fn`` / ``step``) puts a
+second network ``rho``, ``NNBlock(1, 3, 128)``, behind the pooled sum; it is
+``ConditionNet(1, batch_norm=False, pool=None)``, and
+``backward(gc, input_grad=True)`` sends its ``d loss / d x`` on as ``phi``'s
+``gc``::
+
+    c  = pt.forward(Xd, off_d, seed=epoch)      # phi
+    yp = rt.forward(c)                          # rho
+    pt.step(rt.step(gy, input_grad=True))       # gy = d loss / d yp
+
+:func:`segment_repeat` is ``jnp.repeat(c, sizes, axis=0)`` of
+``DeepSetFlow.sample`` on the device, :func:`segment_sum` its reverse.
+
 No JAX is at hand here, so flax.linen's BatchNorm, Dense and Dropout are
 restated from their published definitions, as the couplings' layers are;
 ``jax.random``'s dropout bits are not reproduced (the mask is
@@ -38,7 +51,8 @@ from .activations import act_code, swish
 from .module import Module, lecun_normal, scope_for
 from .optim import Chain
 
-__all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "clamp_offsets", "dropout_keep"]
+__all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "clamp_offsets", "dropout_keep", "segment_repeat",
+           "segment_sum"]
 
 _U64 = (1 << 64) - 1
 
@@ -94,6 +108,109 @@ def dropout_keep(seed: int, rows, cols: int, rate: float) -> np.ndarray:
         k1 = np.uint64((int(k1) + W1) & 0xFFFFFFFF)
     u = (c[L.ZF_DROPOUT_WORD] >> np.uint64(8)).astype(np.float32) * np.float32(2.0**-24)
     return u >= np.float32(rate)
+
+
+def _shape2(a, what: str) -> Tuple[int, int]:
+    """(rows, columns) of a 2-D float32 DeviceArray or of a host array, before anything is copied."""
+    if isinstance(a, DeviceArray):
+        if a.ndim != 2 or a.dtype != np.float32:
+            raise ValueError(f"{what} must be a 2-D float32 DeviceArray, got {a.dtype} {a.shape}")
+        return int(a.shape[0]), int(a.shape[1])
+    shape = np.shape(a)
+    if len(shape) != 2:
+        raise ValueError(f"{what} must be 2-D, got {shape}")
+    return int(shape[0]), int(shape[1])
+
+
+def _to_device2(a) -> DeviceArray:
+    return a if isinstance(a, DeviceArray) else DeviceArray.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
+
+
+def _segment_offsets(offsets, sets: Optional[int], rows: int):
+    """Device offsets as they are (the kernel clamps them), host offsets
+    validated (:func:`check_offsets`); ``sets`` (when known) fixes their
+    number.  Nothing is copied to the device here."""
+    if isinstance(offsets, DeviceArray):
+        if offsets.ndim != 1 or offsets.dtype != np.int64 or offsets.shape[0] < 1:
+            raise ValueError(f"device offsets must be 1-D int64 (S + 1 entries), got {offsets.dtype} {offsets.shape}")
+        off = offsets
+    else:
+        off = check_offsets(offsets, rows)
+    if sets is not None and off.shape[0] != sets + 1:
+        raise ValueError(f"{sets} sets need {sets + 1} offsets, got {off.shape[0]}")
+    return off
+
+
+def repeats_to_offsets(repeats, sets: int) -> np.ndarray:
+    """``repeats`` of ``np.repeat(c, repeats, axis=0)`` for ``sets`` rows (one
+    non-negative int, or one per row) as the S + 1 int64 offsets of
+    :func:`segment_repeat`."""
+    r = np.asarray(repeats)
+    if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != sets):
+        raise ValueError(f"repeats must be an int or {sets} ints, got shape {r.shape}")
+    if not np.issubdtype(r.dtype, np.integer):
+        if not np.all(r == np.floor(r)):
+            raise ValueError("repeats must be integers")
+    r = np.broadcast_to(r.astype(np.int64), (sets,))
+    if (r < 0).any():
+        raise ValueError("repeats must not be negative")
+    return np.concatenate([np.zeros(1, np.int64), np.cumsum(r, dtype=np.int64)])
+
+
+def segment_repeat(c, offsets=None, *, repeats=None, rows: Optional[int] = None):
+    """``jnp.repeat(c, sizes, axis=0)`` of the notebook's
+    ``DeepSetFlow.sample`` on the device (zf_segment_repeat): ``c`` (S, F <=
+    64) -> (rows, F) with ``out[i] = c[set(i)]`` and zeros for rows in no
+    set.  The copies are given either as ``repeats`` (an int, or S
+    non-negative ints; ``rows`` defaults to their sum) or as CSR ``offsets``
+    (S + 1; host offsets are validated with :func:`check_offsets` and ``rows``
+    defaults to the last one, device offsets (an int64 DeviceArray) are only
+    clamped by the kernel and need ``rows``).  Host array in, host array out;
+    DeviceArray in, DeviceArray out.  Its reverse is :func:`segment_sum`."""
+    if (offsets is None) == (repeats is None):
+        raise ValueError("segment_repeat takes either offsets or repeats" +
+                         (", not both" if offsets is not None else ""))
+    S, F = _shape2(c, "c")
+    if repeats is not None:
+        off = repeats_to_offsets(repeats, S)
+        rows = int(off[-1]) if rows is None else int(rows)
+        if rows < off[-1]:
+            raise ValueError(f"repeats make {int(off[-1])} rows, rows = {rows}")
+    else:
+        if rows is None:
+            if isinstance(offsets, DeviceArray):
+                raise ValueError("device offsets are not read back: give rows")
+            rows = int(np.asarray(offsets).reshape(-1)[-1]) if np.size(offsets) else 0
+        rows = int(rows)
+        if rows < 0:
+            raise ValueError(f"rows must not be negative, got {rows}")
+        off = _segment_offsets(offsets, S, rows)
+    L.ensure_device()
+    lib = L.load_library()
+    cd, od = _to_device2(c), _device_offsets(off)
+    out = DeviceArray((rows, F))
+    ws = DeviceArray((max(1, lib.zf_segment_workspace_bytes(rows, S, F)),), np.uint8)
+    check(lib.zf_segment_repeat(cd.ptr, S, F, od.ptr, rows, out.ptr, None, ws.ptr, L.stream()), "zf_segment_repeat")
+    return out if isinstance(c, DeviceArray) else out.numpy()
+
+
+def segment_sum(h, offsets):
+    """The sum over each set's rows (zf_segment_sum, no dropout): ``h`` (rows,
+    F <= 64) and S + 1 ``offsets`` -> (S, F); the reverse of
+    :func:`segment_repeat` and the pooling of :class:`ConditionNet`, with its
+    fixed order of additions.  Host offsets are validated, device offsets only
+    clamped by the kernel.  Host array in, host array out; DeviceArray in,
+    DeviceArray out."""
+    rows, F = _shape2(h, "h")
+    off = _segment_offsets(offsets, None, rows)
+    S = off.shape[0] - 1
+    L.ensure_device()
+    lib = L.load_library()
+    hd, od = _to_device2(h), _device_offsets(off)
+    out = DeviceArray((S, F))
+    ws = DeviceArray((max(1, lib.zf_segment_workspace_bytes(rows, S, F)),), np.uint8)
+    check(lib.zf_segment_sum(hd.ptr, rows, F, od.ptr, S, 0.0, 0, out.ptr, None, ws.ptr, L.stream()), "zf_segment_sum")
+    return out if isinstance(h, DeviceArray) else out.numpy()
 
 
 class _Layout:
@@ -381,8 +498,18 @@ class ConditionTrainer:
         ct.step(gc)
 
     and likewise with the ``d / d c`` of ``tr.sample_backward`` or
-    ``tr.log_prob_vjp``.  Not provided: data parallelism, graph capture,
-    saving the optimiser state, ``d / d x``."""
+    ``tr.log_prob_vjp``.  A network behind this one (the notebook's ``rho``
+    behind ``phi``, ``class DeepSet``) is a second trainer whose
+    ``backward(gy, input_grad=True)`` or ``step(gy, input_grad=True)`` returns
+    the ``d loss / d x`` that is this one's ``gc``::
+
+        c = pt.forward(Xd, off_d, seed=epoch)
+        yp = rt.forward(c)
+        pt.step(rt.step(gy, input_grad=True))
+
+    Not provided: eval-mode input gradients (an eval forward leaves nothing
+    pending), data parallelism, graph capture, saving the optimiser state,
+    pooling other than the sum."""
 
     def __init__(self, net: ConditionNet, variables: Dict[str, Any], in_dim: int, rows_max: int,
                  sets_max: Optional[int] = None, optimizer=None):
@@ -410,7 +537,7 @@ class ConditionTrainer:
             check(L.load_library().zf_condnet_set_optim_chain(
                 self._h.ptr, ct.byref(lowered), None if dmask is None else dmask.ctypes.data),
                 "zf_condnet_set_optim_chain")
-        self._pending: Optional[Tuple[int, int]] = None  # (rows of c, device result?)
+        self._pending: Optional[Tuple[int, bool, int]] = None  # (rows of c, device result?, rows of x)
         self._last_grad: Optional[DeviceArray] = None
 
     @property
@@ -455,20 +582,25 @@ class ConditionTrainer:
         self._pending = None
         out = self._h.forward(xd, off, train, update_stats, seed)
         if train:
-            self._pending = (out.shape[0], x_dev)
+            self._pending = (out.shape[0], x_dev, rows)
         return out if x_dev else out.numpy()
 
-    def backward(self, gc):
+    def backward(self, gc, *, input_grad: bool = False):
         """The gradient, in the blob layout, of the loss whose ``d loss / d c``
         is ``gc`` (the shape of the pending forward's result; a host array or
         a float32 DeviceArray) with respect to the network's parameters
         (zf_condnet_backward; :meth:`grad_tree` makes a ``params`` tree of
         it).  A DeviceArray when ``forward`` was given one.  One backward per
-        train-mode forward: ValueError otherwise."""
+        train-mode forward: ValueError otherwise.
+
+        ``input_grad=True`` returns ``(g, gx)`` with ``gx`` (rows, in_dim)
+        float32 the ``d loss / d x`` of the pending pass
+        (zf_condnet_backward_input), on the device or the host as ``g`` is;
+        ``g`` has the same bits either way."""
         if self._pending is None:
             raise ValueError("backward needs a pending train-mode forward (one backward per forward; an eval-mode "
                              "forward and apply_gradient leave none)")
-        n, dev = self._pending
+        n, dev, rows = self._pending
         F = self.net.features
         if isinstance(gc, DeviceArray):
             if gc.dtype != np.float32 or int(np.prod(gc.shape)) != n * F:
@@ -481,9 +613,15 @@ class ConditionTrainer:
             gd = DeviceArray.from_numpy(np.ascontiguousarray(a.reshape(n, F)))
         g = DeviceArray((self.layout.size,))
         self._pending = None
-        check(L.load_library().zf_condnet_backward(self._h.ptr, gd.ptr, g.ptr, L.stream()), "zf_condnet_backward")
+        if not input_grad:
+            check(L.load_library().zf_condnet_backward(self._h.ptr, gd.ptr, g.ptr, L.stream()), "zf_condnet_backward")
+            self._last_grad = g
+            return g if dev else g.numpy()
+        gx = DeviceArray((rows, self.in_dim))
+        check(L.load_library().zf_condnet_backward_input(self._h.ptr, gd.ptr, g.ptr, gx.ptr, L.stream()),
+              "zf_condnet_backward_input")
         self._last_grad = g
-        return g if dev else g.numpy()
+        return (g, gx) if dev else (g.numpy(), gx.numpy())
 
     def apply_gradient(self, g=None) -> None:
         """The optimiser update on ``g`` (zf_condnet_apply_gradient): a
@@ -506,11 +644,18 @@ class ConditionTrainer:
         check(L.load_library().zf_condnet_apply_gradient(self._h.ptr, None if gd is None else gd.ptr, L.stream()),
               "zf_condnet_apply_gradient")
 
-    def step(self, gc) -> None:
+    def step(self, gc, *, input_grad: bool = False):
         """:meth:`backward` then :meth:`apply_gradient`: one optimiser step on
-        the gradient that ``gc`` sends back."""
-        self.backward(gc)
+        the gradient that ``gc`` sends back.  ``input_grad=True`` returns the
+        ``gx`` of :meth:`backward`, formed before the update from the
+        pre-update parameters; None otherwise."""
+        if not input_grad:
+            self.backward(gc)
+            self.apply_gradient()
+            return None
+        _, gx = self.backward(gc, input_grad=True)
         self.apply_gradient()
+        return gx
 
     def variables(self) -> Dict[str, Any]:
         """The current ``params`` and ``batch_stats`` trees."""
