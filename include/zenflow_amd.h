@@ -696,6 +696,54 @@ int zf_segment_sum(const float* h, int64_t rows, int F, const int64_t* off, int6
 int zf_segment_bcast(const float* gc, const int32_t* set_index, int64_t rows, int F, int64_t sets, float rate,
                      uint64_t seed, float* g_h, void* stream);
 
+/* Mean and max over ragged sets — replace `jnp.mean(x, axis=...)` /
+ * `jnp.max(x, axis=...)` over a set's rows in Phi.__call__, where a user of
+ * the reference edits the pooling line (deep sets' three standard
+ * reductions; the max is PointNet's).  pool: ZF_POOL_SUM | ZF_POOL_MEAN |
+ * ZF_POOL_MAX; d(i, f), the clamped offsets o, n_s = o[s+1] - o[s], rows in no
+ * set and the other arguments as zf_segment_sum's.
+ *   SUM   zf_segment_sum itself: the same launches, the same bits.
+ *   MEAN  out[s, f] = sum_s[f] / (float)n_s, sum_s the bits zf_segment_sum
+ *         returns, one IEEE fp32 division; an empty set gives a row of +0.
+ *   MAX   out[s, f] = max over the set's rows of d(i, f).  A NaN anywhere in
+ *         the (set, column) gives NaN (as jnp.max; fmaxf alone would drop
+ *         it); +-inf are values; an empty set gives a row of +0.  The maximum
+ *         is exact: only the sign of a zero depends on the order.  Dropped
+ *         entries are zeros that take part (Dropout, then the pooling).  The
+ *         levels are the sum's: one wave per ZF_SEG_CHUNK rows, until every
+ *         set is down to one chunk.
+ * count (sets x F int32, or NULL): MEAN n_s in every column; MAX t[s, f], the
+ * number of the set's rows with d(i, f) == out[s, f] (for a NaN maximum the
+ * NaN entries), counted in int32 over one more pass over h; SUM untouched.
+ * workspace: zf_segment_pool_workspace_bytes(rows, sets, F, pool) bytes (0
+ * for arguments the entry rejects).  No atomics: the same bits every call.
+ * Limits and error codes are zf_segment_sum's; ZF_EINVAL also for an unknown
+ * pool.  Nothing is enqueued then. */
+#define ZF_POOL_MEAN 2
+#define ZF_POOL_MAX 3
+int64_t zf_segment_pool_workspace_bytes(int64_t rows, int64_t sets, int F, int pool);
+int zf_segment_pool(const float* h, int64_t rows, int F, const int64_t* off, int64_t sets, int pool, float rate,
+                    uint64_t seed, float* out, int32_t* set_index, int32_t* count, void* workspace, void* stream);
+
+/* Their reverse — the gradient of `jnp.mean` / `jnp.max` over the sets of
+ * Dropout(x) with respect to x:
+ *   MEAN  g_d[i, f] = gc[set(i), f] / (float)n_set(i)
+ *   MAX   g_d[i, f] = d(i, f) == out[s, f] ? gc[s, f] / (float)t[s, f] : 0,
+ *         s = set(i): the gradient is split evenly among ties, the convention
+ *         of jnp.max's gradient and of torch.scatter_reduce(reduce="amax");
+ *         for a NaN maximum the NaN entries are the ties.  With dropout every
+ *         dropped entry of a column whose kept values are all negative ties
+ *         at 0.
+ *   g_h[i, f] = g_d[i, f] * keep(i, f) / (1 - rate), and 0 for rows in no set
+ *   (or whose count is 0), exactly as zf_segment_bcast applies it.
+ * h and out (the forward's input and result) are read for MAX only, count
+ * (the forward's) for MEAN and MAX; SUM is zf_segment_bcast itself.  ZF_EINVAL
+ * for an unknown pool and for a NULL pointer the mode reads; otherwise
+ * zf_segment_bcast's codes. */
+int zf_segment_pool_bcast(const float* gc, const int32_t* set_index, int64_t rows, int F, int64_t sets, int pool,
+                          float rate, uint64_t seed, const float* h, const float* out, const int32_t* count,
+                          float* g_h, void* stream);
+
 /* Repeat over ragged sets — replaces `jnp.repeat(c, sizes, axis=0)` of
  * DeepSetFlow.sample, with the sizes in CSR form (off[s + 1] - off[s] copies
  * of row s):
@@ -727,13 +775,15 @@ int zf_segment_repeat(const float* c, int64_t sets, int F, const int64_t* off, i
 
 #define ZF_POOL_NONE 0 /* one output row per input row (an NNBlock behind BatchNorm) */
 #define ZF_POOL_SUM 1  /* Phi: one output row per set */
+/* ZF_POOL_MAX (3): one output row per set, zf_segment_pool's max.  ZF_POOL_MEAN (2) is a mode of
+ * zf_segment_pool alone: zf_condnet_plan rejects it, as it rejects every other code. */
 
 /* Replaces the configuration of Phi / NNBlock (out_dim, depth, width, act):
  *   BatchNorm(use_running_average=not train)         when batch_norm
  *   Dense(hidden[l]) + act, l = 0 .. n_hidden - 1
  *   Dense(out_dim)
  *   Dropout(dropout, deterministic=not train)
- *   sum over each set's rows                          when pool == ZF_POOL_SUM
+ *   sum / max over each set's rows                    when pool == ZF_POOL_SUM / ZF_POOL_MAX
  * Limits: 1 <= in_dim <= 64, 0 <= n_hidden <= 16, 1 <= hidden[l] <= 4096,
  * 1 <= out_dim <= 64, 0 <= dropout < 1 (ZF_ENOTSUP beyond the sizes,
  * ZF_EINVAL for the rest).  The offsets (in floats) into the natural blob are
@@ -781,7 +831,7 @@ int zf_condnet_destroy(zf_condnet_t* handle);
 /* Replaces Phi.__call__(x, sum_matrix, train) (and deep_set_flow.apply(...,
  * train=True, mutable=["batch_stats"], rngs={"dropout": key}) for its phi
  * half): x (rows, in_dim) on the device -> c_out, (sets, out_dim) with
- * ZF_POOL_SUM (off: sets + 1 offsets on the device, as zf_segment_sum's) or
+ * ZF_POOL_SUM / ZF_POOL_MAX (off: sets + 1 offsets on the device, as zf_segment_sum's) or
  * (rows, out_dim) with ZF_POOL_NONE (off must be NULL; sets is ignored).
  *   train != 0  BatchNorm on the statistics of all `rows` rows passed (padding
  *               rows included: what nn.BatchNorm sees in the example), biased
@@ -793,7 +843,7 @@ int zf_condnet_destroy(zf_condnet_t* handle);
  *   train == 0  the stored statistics, no dropout (`seed` is ignored);
  *               update_stats must be 0; nothing stays pending.
  * ZF_EINVAL (nothing enqueued): NULL x / c_out, rows outside [1, rows_max],
- * sets outside [1, sets_max] or a NULL off with ZF_POOL_SUM, a non-NULL off
+ * sets outside [1, sets_max] or a NULL off with a pooled network, a non-NULL off
  * with ZF_POOL_NONE, update_stats without train.  Every call drops a pending
  * pass first. */
 int zf_condnet_forward(zf_condnet_t* handle, const float* x, int64_t rows, const int64_t* off, int64_t sets,

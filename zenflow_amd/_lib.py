@@ -71,6 +71,8 @@ ZF_DROPOUT_STREAM = 0x64726F70
 ZF_DROPOUT_WORD = 0
 ZF_POOL_NONE = 0
 ZF_POOL_SUM = 1
+ZF_POOL_MEAN = 2
+ZF_POOL_MAX = 3
 
 
 class ZfOpDesc(C.Structure):
@@ -219,6 +221,9 @@ SIGNATURES = {
     "zf_segment_workspace_bytes": (_i64, [_i64, _i64, _int]),
     "zf_segment_sum": (_int, [_vp, _i64, _int, _vp, _i64, C.c_float, _u64, _vp, _vp, _vp, _vp]),
     "zf_segment_bcast": (_int, [_vp, _vp, _i64, _int, _i64, C.c_float, _u64, _vp, _vp]),
+    "zf_segment_pool_workspace_bytes": (_i64, [_i64, _i64, _int, _int]),
+    "zf_segment_pool": (_int, [_vp, _i64, _int, _vp, _i64, _int, C.c_float, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "zf_segment_pool_bcast": (_int, [_vp, _vp, _i64, _int, _i64, _int, C.c_float, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zf_segment_repeat": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
     "zf_condnet_backward_input": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "zf_condnet_plan": (_int, [C.POINTER(ZfCondnetDesc), C.POINTER(_i64)]),

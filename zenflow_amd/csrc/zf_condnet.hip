@@ -1,9 +1,9 @@
 // Conditioning networks on the device: the `Phi` of examples/deep_set.ipynb
 // (cells `class NNBlock` / `class Phi` / `class DeepSetFlow` / `loss_fn_2`),
-//   BatchNorm -> (Dense, act) x depth -> Dense -> Dropout -> sum over each set,
+//   BatchNorm -> (Dense, act) x depth -> Dense -> Dropout -> sum (or max) over each set,
 // forward, reverse (parameter and input gradients for a given d loss / d c) and the
 // optimiser update, behind zf_condnet_* (include/zenflow_amd.h); and the
-// standalone segment sum / broadcast / repeat, zf_segment_*.
+// standalone segment sum / mean / max / broadcast / repeat, zf_segment_*.
 //
 // The Dense layers, the weight-gradient trees, BatchNorm and the optimiser
 // are the trainer's, included as they are (zf_gemm.h, zf_reduce.h,
@@ -212,6 +212,188 @@ __global__ __launch_bounds__(kRepRows) void seg_repeat_kernel(const float* __res
   }
 }
 
+// ---- mean and max over each set (jnp.mean / jnp.max in Phi.__call__) -----------------
+// The mask of drop_apply alone: the max's reverse needs d(i, f) and the
+// dropout reverse of the same element, one Philox draw for both.
+template <bool DROP>
+__device__ __forceinline__ bool drop_keep(unsigned long long seed, long long i, int f, float rate) {
+  if (!DROP) return true;
+  return u01_co(philox_at(seed, i, f, ZF_DROPOUT_STREAM).v[ZF_DROPOUT_WORD]) >= rate;
+}
+
+// max(a, b) with a NaN in either making the result NaN (fmaxf drops NaNs): a
+// NaN accumulator stays (both comparisons are false), a NaN b replaces it.
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+
+// d is a maximal entry of a (set, column) whose maximum is m; for a NaN maximum the NaN entries are.
+__device__ __forceinline__ bool is_tie(float d, float m) { return d == m || (m != m && d != d); }
+
+// One level of the max: seg_chunk_sum_kernel with nan_max in place of the
+// addition and -inf in place of +0 (a chunk has at least one row, so no -inf
+// of the start survives; the maximum is exact, the order of the comparisons
+// changes no bit but the sign of a zero).  Dropped entries are zeros that
+// take part (Dropout, then the pooling).
+template <bool DROP>
+__global__ __launch_bounds__(256) void seg_chunk_max_kernel(const float* __restrict__ h, int F, long long S,
+                                                            const long long* __restrict__ o,
+                                                            const long long* __restrict__ cb, float rate,
+                                                            float keep_prob, unsigned long long seed,
+                                                            float* __restrict__ part, float* __restrict__ out,
+                                                            int* __restrict__ set_index) {
+#pragma clang fp contract(off)
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long c = (long long)blockIdx.x * 4 + w;
+  const bool live = c < cb[S];
+  const int R = 64 / F, j = lane / F, f = lane - j * F;
+  float acc = -INFINITY;
+  long long s = 0;
+  bool only = false;
+  if (live) {
+    s = seg_find_set(cb, S, c, lane);
+    only = cb[s + 1] - cb[s] == 1;
+    if (j < R) {
+      const long long r0 = o[s] + (c - cb[s]) * kSegChunk;  // first row of the chunk
+      const int len = (int)min((long long)kSegChunk, o[s + 1] - r0);
+      int r = j;
+      for (; r + 7 * R < len; r += 8 * R) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = h[(r0 + r + u * R) * F + f];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          acc = nan_max(acc, drop_apply<DROP>(v[u], seed, r0 + r + u * R, f, rate, keep_prob));
+      }
+      for (; r < len; r += R) acc = nan_max(acc, drop_apply<DROP>(h[(r0 + r) * F + f], seed, r0 + r, f, rate, keep_prob));
+      if (set_index && f == 0)
+        for (int q = j; q < len; q += R) set_index[r0 + q] = (int)s;
+    }
+  }
+  red[w][lane] = acc;
+  __syncthreads();
+  if (live && lane < F) {
+    float v = red[w][lane];
+    for (int q = 1; q < R; ++q) v = nan_max(v, red[w][q * F + lane]);
+    if (only) out[s * F + lane] = v;
+    else if (part) part[c * F + lane] = v;
+  }
+}
+
+// The tie count of the max, first pass: one wave per chunk of h's rows (the
+// first level's o and cb), lanes (j, f) as above count the chunk's entries
+// with d(i, f) == m[s, f] in int32.  A set's only chunk writes count[s, f]
+// (zeroed before: empty sets), every other chunk row c of `cpart`.
+template <bool DROP>
+__global__ __launch_bounds__(256) void seg_chunk_ties_kernel(const float* __restrict__ h, int F, long long S,
+                                                             const long long* __restrict__ o,
+                                                             const long long* __restrict__ cb, float rate,
+                                                             float keep_prob, unsigned long long seed,
+                                                             const float* __restrict__ m, int* __restrict__ cpart,
+                                                             int* __restrict__ count) {
+  __shared__ int red[4][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long c = (long long)blockIdx.x * 4 + w;
+  const bool live = c < cb[S];
+  const int R = 64 / F, j = lane / F, f = lane - j * F;
+  int acc = 0;
+  long long s = 0;
+  bool only = false;
+  if (live) {
+    s = seg_find_set(cb, S, c, lane);
+    only = cb[s + 1] - cb[s] == 1;
+    if (j < R) {
+      const long long r0 = o[s] + (c - cb[s]) * kSegChunk;
+      const int len = (int)min((long long)kSegChunk, o[s + 1] - r0);
+      const float top = m[s * F + f];
+      int r = j;
+      for (; r + 7 * R < len; r += 8 * R) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = h[(r0 + r + u * R) * F + f];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          acc += is_tie(drop_apply<DROP>(v[u], seed, r0 + r + u * R, f, rate, keep_prob), top) ? 1 : 0;
+      }
+      for (; r < len; r += R)
+        acc += is_tie(drop_apply<DROP>(h[(r0 + r) * F + f], seed, r0 + r, f, rate, keep_prob), top) ? 1 : 0;
+    }
+  }
+  red[w][lane] = acc;
+  __syncthreads();
+  if (live && lane < F) {
+    int v = red[w][lane];
+    for (int q = 1; q < R; ++q) v += red[w][q * F + lane];
+    if (only) count[s * F + lane] = v;
+    else cpart[c * F + lane] = v;
+  }
+}
+
+// Second pass: one wave per set of more than one chunk adds the set's chunk
+// counts, rows cb[s] .. cb[s + 1] - 1 of `cpart` (integers: any order).
+__global__ __launch_bounds__(256) void seg_ties_sum_kernel(const int* __restrict__ cpart, int F, long long S,
+                                                           const long long* __restrict__ cb,
+                                                           int* __restrict__ count) {
+  __shared__ int red[4][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long s = (long long)blockIdx.x * 4 + w;
+  const int R = 64 / F, j = lane / F, f = lane - j * F;
+  const long long c0 = s < S ? cb[s] : 0, n = s < S ? cb[s + 1] - c0 : 0;
+  int acc = 0;
+  if (n > 1 && j < R)
+    for (long long q = j; q < n; q += R) acc += cpart[(c0 + q) * F + f];
+  red[w][lane] = acc;
+  __syncthreads();
+  if (n > 1 && lane < F) {
+    int v = red[w][lane];
+    for (int q = 1; q < R; ++q) v += red[w][q * F + lane];
+    count[s * F + lane] = v;
+  }
+}
+
+// The mean's finish on the sum's result: out[s, f] / (float)n_s, one IEEE
+// division (an empty set keeps its +0), and n_s as the count of every column.
+__global__ void seg_mean_finish_kernel(float* __restrict__ out, int F, long long S, const long long* __restrict__ o,
+                                       int* __restrict__ count) {
+#pragma clang fp contract(off)
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= S * F) return;
+  const long long s = t / F;
+  const long long n = o[s + 1] - o[s];
+  if (n > 0) out[t] = out[t] / (float)n;
+  if (count) count[t] = (int)n;
+}
+
+// ---- their reverse --------------------------------------------------------------------
+// mean: g_d[i, f] = gc[s, f] / (float)n_s;  max: gc[s, f] / (float)t[s, f] on
+// the maximal entries d(i, f) == m[s, f] (an even split among ties, d
+// recomputed from h and the mask), 0 elsewhere; then dropout's reverse, as
+// seg_bcast_kernel applies it.  Rows in no set (and a count of 0) give 0.
+template <bool DROP, bool MAX>
+__global__ void seg_pool_bcast_kernel(const float* __restrict__ gc, const int* __restrict__ idx, long long rows,
+                                      int F, long long S, float rate, float keep_prob, unsigned long long seed,
+                                      const float* __restrict__ h, const float* __restrict__ m,
+                                      const int* __restrict__ count, float* __restrict__ g) {
+#pragma clang fp contract(off)
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= rows * F) return;
+  const long long i = t / F;
+  const int f = (int)(t - i * F);
+  const long long s = idx[i];
+  float v = 0.f;
+  const bool keep = drop_keep<DROP>(seed, i, f, rate);
+  if (s >= 0 && s < S) {
+    const int n = count[s * F + f];
+    bool on = n > 0;
+    if (MAX && on) {
+      const float hv = h[t];
+      const float d = DROP ? (keep ? hv / keep_prob : 0.f) : hv;
+      on = is_tie(d, m[s * F + f]);
+    }
+    if (on) v = gc[s * F + f] / (float)n;
+  }
+  g[t] = DROP ? (keep ? v / keep_prob : 0.f) : v;
+}
+
 // The levels of one segment sum: level 0 sums the chunks of h's rows, level
 // k > 0 those of level k - 1's chunk sums (a set's chunk sums are consecutive
 // rows of `part`, its offsets the chunk counts cb: again sets of rows), until
@@ -245,8 +427,9 @@ int seg_check(const void* a, const void* b, const void* c, long long rows, int F
   return ZF_OK;
 }
 
-int seg_sum_launch(const float* h, long long rows, int F, const long long* off, long long S, float rate,
-                   unsigned long long seed, float* out, int* set_index, void* ws, hipStream_t st) {
+// mx: the levels of the max (seg_chunk_max_kernel) over the same plan, workspace and grids.
+int seg_reduce_launch(const float* h, long long rows, int F, const long long* off, long long S, float rate,
+                      unsigned long long seed, float* out, int* set_index, void* ws, bool mx, hipStream_t st) {
   if (set_index) ZF_TRY_HIP(hipMemsetAsync(set_index, 0xff, (size_t)rows * sizeof(int), st));  // -1: in no set
   if (S == 0) return ZF_OK;
   ZF_TRY_HIP(hipMemsetAsync(out, 0, (size_t)S * F * sizeof(float), st));  // empty sets
@@ -264,19 +447,23 @@ int seg_sum_launch(const float* h, long long rows, int F, const long long* off, 
     const long long chunks = seg_max_chunks(in_rows, S);
     const dim3 grid((unsigned)((chunks + 3) / 4));
     float* dst = k + 1 == L ? nullptr : part;
-    if (k == 0 && rate > 0.f)
-      hipLaunchKernelGGL(seg_chunk_sum_kernel<true>, grid, dim3(256), 0, st, in, F, S, (const long long*)o,
-                         (const long long*)cb, rate, kp, seed, dst, out, set_index);
-    else
-      hipLaunchKernelGGL(seg_chunk_sum_kernel<false>, grid, dim3(256), 0, st, in, F, S, (const long long*)o,
-                         (const long long*)cb, rate, kp, seed, dst, out, k == 0 ? set_index : nullptr);
-    ZF_CHECK_LAUNCH("seg_chunk_sum_kernel");
+    const bool drop = k == 0 && rate > 0.f;
+    auto* const kernel = mx ? (drop ? seg_chunk_max_kernel<true> : seg_chunk_max_kernel<false>)
+                            : (drop ? seg_chunk_sum_kernel<true> : seg_chunk_sum_kernel<false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, in, F, S, (const long long*)o, (const long long*)cb, rate, kp,
+                       seed, dst, out, k == 0 ? set_index : nullptr);
+    ZF_CHECK_LAUNCH(mx ? "seg_chunk_max_kernel" : "seg_chunk_sum_kernel");
     in = part;
     in_rows = chunks;
     off = cb;
     part += chunks * F;
   }
   return ZF_OK;
+}
+
+int seg_sum_launch(const float* h, long long rows, int F, const long long* off, long long S, float rate,
+                   unsigned long long seed, float* out, int* set_index, void* ws, hipStream_t st) {
+  return seg_reduce_launch(h, rows, F, off, S, rate, seed, out, set_index, ws, false, st);
 }
 
 int seg_bcast_launch(const float* gc, const int* idx, long long rows, int F, long long S, float rate,
@@ -311,6 +498,62 @@ int seg_repeat_launch(const float* c, long long S, int F, const long long* off, 
   return ZF_OK;
 }
 
+inline bool seg_pool_known(int pool) { return pool == ZF_POOL_SUM || pool == ZF_POOL_MEAN || pool == ZF_POOL_MAX; }
+
+// The reduction's workspace and, for the max, the first level's chunk tie counts behind it.
+inline long long seg_pool_ws_bytes(long long rows, long long S, int F, int pool) {
+  long long bytes = seg_ws_bytes(rows, S, F);
+  if (pool == ZF_POOL_MAX) bytes += seg_max_chunks(rows, S) * F * (long long)sizeof(int);
+  return bytes;
+}
+
+// sum: seg_sum_launch.  mean: the same launches, then the divide.  max: the
+// max's levels, then (with count) the two tie-count passes over the first
+// level's plan, which the levels leave in the workspace.
+int seg_pool_launch(const float* h, long long rows, int F, const long long* off, long long S, int pool, float rate,
+                    unsigned long long seed, float* out, int* set_index, int* count, void* ws, hipStream_t st) {
+  const int rc = seg_reduce_launch(h, rows, F, off, S, rate, seed, out, set_index, ws, pool == ZF_POOL_MAX, st);
+  if (rc || S == 0 || pool == ZF_POOL_SUM) return rc;
+  const long long* o = (const long long*)ws;
+  const long long* cb = o + (S + 1);
+  if (pool == ZF_POOL_MEAN) {
+    hipLaunchKernelGGL(seg_mean_finish_kernel, dim3(blocks_for(S * F)), dim3(256), 0, st, out, F, S, o, count);
+    ZF_CHECK_LAUNCH("seg_mean_finish_kernel");
+    return ZF_OK;
+  }
+  if (!count) return ZF_OK;
+  ZF_TRY_HIP(hipMemsetAsync(count, 0, (size_t)S * F * sizeof(int), st));  // empty sets
+  int* cpart = (int*)((char*)ws + seg_ws_bytes(rows, S, F));
+  const float kp = 1.0f - rate;
+  const dim3 grid((unsigned)((seg_max_chunks(rows, S) + 3) / 4));
+  if (rate > 0.f)
+    hipLaunchKernelGGL(seg_chunk_ties_kernel<true>, grid, dim3(256), 0, st, h, F, S, o, cb, rate, kp, seed,
+                       (const float*)out, cpart, count);
+  else
+    hipLaunchKernelGGL(seg_chunk_ties_kernel<false>, grid, dim3(256), 0, st, h, F, S, o, cb, rate, kp, seed,
+                       (const float*)out, cpart, count);
+  ZF_CHECK_LAUNCH("seg_chunk_ties_kernel");
+  hipLaunchKernelGGL(seg_ties_sum_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, (const int*)cpart, F, S, cb,
+                     count);
+  ZF_CHECK_LAUNCH("seg_ties_sum_kernel");
+  return ZF_OK;
+}
+
+int seg_pool_bcast_launch(const float* gc, const int* idx, long long rows, int F, long long S, int pool, float rate,
+                          unsigned long long seed, const float* h, const float* m, const int* count, float* g,
+                          hipStream_t st) {
+  if (pool == ZF_POOL_SUM) return seg_bcast_launch(gc, idx, rows, F, S, rate, seed, g, st);
+  if (rows == 0) return ZF_OK;
+  const float kp = 1.0f - rate;
+  const bool mx = pool == ZF_POOL_MAX, drop = rate > 0.f;
+  auto* const kernel = mx ? (drop ? seg_pool_bcast_kernel<true, true> : seg_pool_bcast_kernel<false, true>)
+                          : (drop ? seg_pool_bcast_kernel<true, false> : seg_pool_bcast_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(rows * F)), dim3(256), 0, st, gc, idx, rows, F, S, rate, kp, seed, h, m,
+                     count, g);
+  ZF_CHECK_LAUNCH("seg_pool_bcast_kernel");
+  return ZF_OK;
+}
+
 }  // namespace
 }  // namespace zf
 
@@ -336,6 +579,8 @@ struct zf_condnet {
   float* d_gb = nullptr;
   float* d_gu = nullptr;     // [rows_max][in] d / d BatchNorm's output
   int* d_set = nullptr;      // [rows_max] set(i)
+  float* d_pool = nullptr;   // [sets_max][F] the pooled result (max: the reverse compares against it)
+  int* d_cnt = nullptr;      // [sets_max][F] max: its tie counts
   void* d_segws = nullptr;
   double* d_leaf = nullptr;
   double* d_leaf2 = nullptr;
@@ -410,6 +655,10 @@ int cn_ensure_train(zf_condnet* h) {
   h->d_ga = cn_alloc<float>(h, B * wmax, rc);
   h->d_gb = cn_alloc<float>(h, B * wmax, rc);
   h->d_set = cn_alloc<int>(h, B, rc);
+  if (h->desc.pool == ZF_POOL_MAX) {
+    h->d_pool = cn_alloc<float>(h, h->sets_max * h->F, rc);
+    h->d_cnt = cn_alloc<int>(h, h->sets_max * h->F, rc);
+  }
   h->d_leaf = cn_alloc<double>(h, (int64_t)kLeafCap * 128, rc);
   h->d_leaf2 = cn_alloc<double>(h, (int64_t)(kLeafCap / kMaxLeaves) * 128, rc);
   h->d_roots = cn_alloc<double>(h, 256, rc);
@@ -516,7 +765,7 @@ int cn_dense_fwd(zf_condnet* h, const float* in, int B, int train, float* out_la
 
 int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long long S, int train, int update_stats,
                unsigned long long seed, float* c_out, hipStream_t st) {
-  const bool pool = h->desc.pool == ZF_POOL_SUM;
+  const bool pool = h->desc.pool != ZF_POOL_NONE;
   const float rate = train ? h->desc.dropout : 0.f;
   int rc;
   const float* in0 = x;
@@ -530,7 +779,14 @@ int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long 
   // per-row output without dropout: the last Dense writes c_out itself
   float* hl = (!pool && rate == 0.f) ? c_out : h->d_h;
   if ((rc = cn_dense_fwd(h, in0, B, train, hl, st))) return rc;
-  if (pool) return seg_sum_launch(hl, B, h->F, off, S, rate, seed, c_out, train ? h->d_set : nullptr, h->d_segws, st);
+  if (pool) {
+    rc = seg_pool_launch(hl, B, h->F, off, S, h->desc.pool, rate, seed, c_out, train ? h->d_set : nullptr,
+                         train ? h->d_cnt : nullptr, h->d_segws, st);
+    if (rc || !train || h->desc.pool != ZF_POOL_MAX) return rc;
+    // the reverse reads the maxima after the caller's c_out may be gone
+    ZF_TRY_HIP(hipMemcpyAsync(h->d_pool, c_out, (size_t)S * h->F * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return ZF_OK;
+  }
   if (rate > 0.f) return seg_bcast_launch(hl, nullptr, B, h->F, B, rate, seed, c_out, st);
   return ZF_OK;
 }
@@ -544,12 +800,14 @@ int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long 
 // reverse on the column sums the scale and bias gradients reduce anyway.
 int cn_backward(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, hipStream_t st) {
   const int B = (int)h->pend_rows;
-  const bool pool = h->desc.pool == ZF_POOL_SUM;
+  const bool pool = h->desc.pool != ZF_POOL_NONE;
   const float rate = h->desc.dropout;
   int rc;
   const float* gout = gc;
   if (pool) {
-    if ((rc = seg_bcast_launch(gc, h->d_set, B, h->F, h->pend_sets, rate, h->pend_seed, h->d_gl, st))) return rc;
+    rc = seg_pool_bcast_launch(gc, h->d_set, B, h->F, h->pend_sets, h->desc.pool, rate, h->pend_seed, h->d_h,
+                               h->d_pool, h->d_cnt, h->d_gl, st);
+    if (rc) return rc;
     gout = h->d_gl;
   } else if (rate > 0.f) {
     if ((rc = seg_bcast_launch(gc, nullptr, B, h->F, B, rate, h->pend_seed, h->d_gl, st))) return rc;
@@ -643,6 +901,33 @@ int zf_segment_bcast(const float* gc, const int32_t* set_index, int64_t rows, in
   return zf::seg_bcast_launch(gc, set_index, rows, F, sets, rate, seed, g_h, (hipStream_t)stream);
 }
 
+int64_t zf_segment_pool_workspace_bytes(int64_t rows, int64_t sets, int F, int pool) {
+  if (rows < 0 || sets < 0 || F < 1 || F > 64 || !zf::seg_pool_known(pool)) return 0;
+  return zf::seg_pool_ws_bytes(rows, sets, F, pool);
+}
+
+int zf_segment_pool(const float* h, int64_t rows, int F, const int64_t* off, int64_t sets, int pool, float rate,
+                    uint64_t seed, float* out, int32_t* set_index, int32_t* count, void* workspace, void* stream) {
+  if (!zf::seg_pool_known(pool)) return zf::einval("segment: unknown pool %d", pool);
+  const int rc = zf::seg_check(h, off, out, rows, F, sets, rate);
+  if (rc) return rc;
+  if (!workspace) return zf::einval("segment: NULL workspace");
+  return zf::seg_pool_launch(h, rows, F, (const long long*)off, sets, pool, rate, seed, out, set_index, count,
+                             workspace, (hipStream_t)stream);
+}
+
+int zf_segment_pool_bcast(const float* gc, const int32_t* set_index, int64_t rows, int F, int64_t sets, int pool,
+                          float rate, uint64_t seed, const float* h, const float* out, const int32_t* count,
+                          float* g_h, void* stream) {
+  if (!zf::seg_pool_known(pool)) return zf::einval("segment: unknown pool %d", pool);
+  const int rc = zf::seg_check(gc, set_index, g_h, rows, F, sets, rate);
+  if (rc) return rc;
+  if (pool != ZF_POOL_SUM && !count) return zf::einval("segment: NULL count");
+  if (pool == ZF_POOL_MAX && (!h || !out)) return zf::einval("segment: the max's reverse needs h and out");
+  return zf::seg_pool_bcast_launch(gc, set_index, rows, F, sets, pool, rate, seed, h, out, count, g_h,
+                                   (hipStream_t)stream);
+}
+
 int zf_segment_repeat(const float* c, int64_t sets, int F, const int64_t* off, int64_t rows, float* out,
                       int32_t* set_index, void* workspace, void* stream) {
   const int rc = zf::seg_check(c, off, out, rows, F, sets, 0.f);
@@ -665,7 +950,9 @@ int zf_condnet_plan(zf_condnet_desc* d, int64_t* blob_floats) {
     if (d->hidden[l] > 4096) return zf::enotsup("condnet: a hidden width above 4096");
   }
   if (d->act < 0 || d->act >= ZF_ACT_COUNT) return zf::einval("condnet: unknown activation %d", d->act);
-  if (d->pool != ZF_POOL_NONE && d->pool != ZF_POOL_SUM) return zf::einval("condnet: unknown pool %d", d->pool);
+  // (the mean is a standalone reduction only, zf_segment_pool: a network rejects its code as it always has)
+  if (d->pool != ZF_POOL_NONE && d->pool != ZF_POOL_SUM && d->pool != ZF_POOL_MAX)
+    return zf::einval("condnet: unknown pool %d", d->pool);
   if (!(d->dropout >= 0.f && d->dropout < 1.f)) return zf::einval("condnet: dropout %g outside [0, 1)", (double)d->dropout);
   if (d->batch_norm != 0 && d->batch_norm != 1) return zf::einval("condnet: batch_norm %d", d->batch_norm);
   int64_t at = 0;
@@ -699,7 +986,7 @@ int zf_condnet_create(const zf_condnet_desc* desc_in, const float* blob_host, in
   if (need != blob_floats)
     return zf::einval("blob has %lld floats, plan needs %lld", (long long)blob_floats, (long long)need);
   if (rows_max < 1 || rows_max > (1 << 24)) return zf::einval("rows_max outside [1, 2^24]");
-  const bool pool = desc.pool == ZF_POOL_SUM;
+  const bool pool = desc.pool != ZF_POOL_NONE;
   if (pool && (sets_max < 1 || sets_max > zf::kSegMaxSets)) return zf::einval("sets_max outside [1, 2^24]");
   const zf_optim_desc dflt{1e-3f, 0.9f, 0.999f, 1e-8f, 1e-4f, 1};
   const zf_optim_chain chain = zf::adamw_chain(optim ? *optim : dflt);
@@ -725,7 +1012,7 @@ int zf_condnet_create(const zf_condnet_desc* desc_in, const float* blob_host, in
   h->d_rstd = zf::cn_alloc<float>(h, 64, rc);
   for (int l = 0; l < h->L; ++l) h->H.push_back(zf::cn_alloc<float>(h, B * desc.hidden[l], rc));
   h->d_h = zf::cn_alloc<float>(h, B * h->F, rc);
-  h->d_segws = zf::cn_alloc<char>(h, zf::seg_ws_bytes(B, h->sets_max, h->F), rc);
+  h->d_segws = zf::cn_alloc<char>(h, zf::seg_pool_ws_bytes(B, h->sets_max, h->F, desc.pool), rc);
   h->d_split = zf::cn_alloc<float>(h, zf::kSplitFloats, rc);
   hipError_t e = hipSuccess;
   if (!rc) e = hipMemcpy(h->d_nat, blob_host, need * sizeof(float), hipMemcpyHostToDevice);
@@ -756,7 +1043,7 @@ int zf_condnet_forward(zf_condnet_t* h, const float* x, int64_t rows, const int6
   if (!x || !c_out) return zf::einval("NULL argument");
   if (rows < 1 || rows > h->rows_max)
     return zf::einval("rows %lld outside [1, rows_max = %lld]", (long long)rows, (long long)h->rows_max);
-  const bool pool = h->desc.pool == ZF_POOL_SUM;
+  const bool pool = h->desc.pool != ZF_POOL_NONE;
   if (pool) {
     if (!off) return zf::einval("a pooled network needs the sets' offsets");
     if (sets < 1 || sets > h->sets_max)

@@ -5,6 +5,8 @@ turns the elements of each set into the flow's condition,
 
     BatchNorm -> (Dense, act) x depth -> Dense -> Dropout -> sum over each set
 
+(or, where a user of the reference edits that line of ``Phi.__call__`` to
+``jnp.max``, the max over each set: ``pool="max"``)
 (cells ``class NNBlock`` / ``class Phi`` / ``class DeepSetFlow`` /
 ``loss_fn_2``).  :class:`ConditionNet` is that network as a module of this
 package's protocol, usable where the notebook puts ``Phi()``;
@@ -30,7 +32,9 @@ second network ``rho``, ``NNBlock(1, 3, 128)``, behind the pooled sum; it is
     pt.step(rt.step(gy, input_grad=True))       # gy = d loss / d yp
 
 :func:`segment_repeat` is ``jnp.repeat(c, sizes, axis=0)`` of
-``DeepSetFlow.sample`` on the device, :func:`segment_sum` its reverse.
+``DeepSetFlow.sample`` on the device, :func:`segment_sum` its reverse;
+:func:`segment_mean` and :func:`segment_max` are the other two poolings on
+their own.
 
 No JAX is at hand here, so flax.linen's BatchNorm, Dense and Dropout are
 restated from their published definitions, as the couplings' layers are;
@@ -51,10 +55,11 @@ from .activations import act_code, swish
 from .module import Module, lecun_normal, scope_for
 from .optim import Chain
 
-__all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "clamp_offsets", "dropout_keep", "segment_repeat",
-           "segment_sum"]
+__all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "clamp_offsets", "dropout_keep", "segment_max",
+           "segment_mean", "segment_repeat", "segment_sum"]
 
 _U64 = (1 << 64) - 1
+_POOLS = {None: L.ZF_POOL_NONE, "sum": L.ZF_POOL_SUM, "max": L.ZF_POOL_MAX}
 
 
 def check_offsets(offsets, rows: int) -> np.ndarray:
@@ -213,6 +218,36 @@ def segment_sum(h, offsets):
     return out if isinstance(h, DeviceArray) else out.numpy()
 
 
+def _segment_pool(h, offsets, pool: int):
+    rows, F = _shape2(h, "h")
+    off = _segment_offsets(offsets, None, rows)
+    S = off.shape[0] - 1
+    L.ensure_device()
+    lib = L.load_library()
+    hd, od = _to_device2(h), _device_offsets(off)
+    out = DeviceArray((S, F))
+    ws = DeviceArray((max(1, lib.zf_segment_pool_workspace_bytes(rows, S, F, pool)),), np.uint8)
+    check(lib.zf_segment_pool(hd.ptr, rows, F, od.ptr, S, pool, 0.0, 0, out.ptr, None, None, ws.ptr, L.stream()),
+          "zf_segment_pool")
+    return out if isinstance(h, DeviceArray) else out.numpy()
+
+
+def segment_mean(h, offsets):
+    """The mean over each set's rows (zf_segment_pool, ZF_POOL_MEAN, no
+    dropout): :func:`segment_sum`'s result divided by the set's number of rows
+    in one fp32 division, a zero row for an empty set.  Arguments and
+    conventions as :func:`segment_sum`'s."""
+    return _segment_pool(h, offsets, L.ZF_POOL_MEAN)
+
+
+def segment_max(h, offsets):
+    """The maximum over each set's rows (zf_segment_pool, ZF_POOL_MAX, no
+    dropout): exact, a NaN in a (set, column) gives NaN there as ``jnp.max``
+    does, a zero row for an empty set.  Arguments and conventions as
+    :func:`segment_sum`'s."""
+    return _segment_pool(h, offsets, L.ZF_POOL_MAX)
+
+
 class _Layout:
     """The natural blob of a ConditionNet for ``in_dim`` input columns
     (zf_condnet_plan): descriptor, and blob <-> variable trees."""
@@ -232,7 +267,7 @@ class _Layout:
         d.out_dim = int(net.features)
         d.act = act_code(net.act)
         d.batch_norm = 1 if net.batch_norm else 0
-        d.pool = L.ZF_POOL_SUM if net.pool == "sum" else L.ZF_POOL_NONE
+        d.pool = _POOLS[net.pool]
         d.dropout = float(net.dropout)
         n = ct.c_int64()
         check(L.load_library().zf_condnet_plan(ct.byref(d), ct.byref(n)), "zf_condnet_plan")
@@ -315,7 +350,7 @@ class _Handle:
 
     @property
     def pooled(self) -> bool:
-        return self.layout.desc.pool == L.ZF_POOL_SUM
+        return self.layout.desc.pool != L.ZF_POOL_NONE
 
     def forward(self, xd: DeviceArray, off: Optional[DeviceArray], train: bool, update_stats: bool, seed: int):
         rows = xd.shape[0]
@@ -356,7 +391,7 @@ def _check_offsets_arg(offsets, rows: int, pooled: bool):
             raise ValueError("offsets given to a network without pooling (pool=None)")
         return None
     if offsets is None:
-        raise ValueError('a network with pool="sum" needs the sets\' offsets')
+        raise ValueError("a pooled network needs the sets' offsets")
     if isinstance(offsets, DeviceArray):
         if offsets.ndim != 1 or offsets.dtype != np.int64 or offsets.shape[0] < 2:
             raise ValueError(f"device offsets must be 1-D int64 with S + 1 >= 2 entries, got {offsets.dtype} "
@@ -372,10 +407,13 @@ def _device_offsets(off) -> Optional[DeviceArray]:
 class ConditionNet(Module):
     """``Phi`` of examples/deep_set.ipynb: BatchNorm, ``len(layers)`` Dense
     layers with ``act``, a Dense layer to ``features`` columns, Dropout, and
-    with ``pool="sum"`` the sum over each set's rows.
+    with ``pool="sum"`` / ``"max"`` that reduction over each
+    set's rows (an empty set gives a zero row; the max passes a NaN on as
+    ``jnp.max`` does and splits its gradient evenly among ties, dropped
+    entries being zeros that take part).
 
     ``__call__(x, offsets=None, *, train=False, seed=0)``: ``x`` (rows,
-    in_dim) -> (S, features) with ``pool="sum"`` (``offsets``: S + 1
+    in_dim) -> (S, features) when pooled (``offsets``: S + 1
     non-decreasing integers, host offsets are validated with ValueError,
     device offsets (an int64 DeviceArray) only clamped by the kernel) or
     (rows, features) with ``pool=None``.  Host arrays in, host arrays out;
@@ -384,16 +422,16 @@ class ConditionNet(Module):
     BatchNorm sees them), draws the dropout mask from ``seed`` and needs
     ``mutable=["batch_stats"]`` when the network has a BatchNorm.
 
-    The variables have the notebook's layout, so a tree trained with the
-    reference's ``Phi`` loads unchanged: ``params``: ``BatchNorm_0/{scale,
+    The variables have the notebook's layout whatever the pooling, so a tree
+    trained with the reference's ``Phi`` loads unchanged: ``params``: ``BatchNorm_0/{scale,
     bias}``, ``NNBlock_0/Dense_k/{kernel, bias}``; ``batch_stats``:
     ``BatchNorm_0/{mean, var}`` (no BatchNorm entries with
     ``batch_norm=False``)."""
 
     def __init__(self, features: int, layers: Sequence[int] = (128, 128, 128), act: Union[str, Callable] = swish,
                  batch_norm: bool = True, dropout: float = 0.0, pool: Optional[str] = None):
-        if pool not in (None, "sum"):
-            raise NotImplementedError(f'pool={pool!r}: only None and "sum" are implemented')
+        if pool not in _POOLS:
+            raise NotImplementedError(f'pool={pool!r}: only None, "sum" and "max" are implemented')
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout rate {dropout} outside [0, 1)")
         if int(features) < 1:
@@ -457,13 +495,13 @@ class ConditionNet(Module):
         if scope.initializing:  # inside an outer module's init: create variables only
             scope.init_module(self, in_dim, 0)
             n_out = rows
-            if self.pool == "sum":
+            if self.pool is not None:
                 if offsets is None:
-                    raise ValueError('a network with pool="sum" needs the sets\' offsets')
+                    raise ValueError("a pooled network needs the sets' offsets")
                 n_out = int((offsets.shape if isinstance(offsets, DeviceArray) else np.shape(offsets))[0]) - 1
             return np.zeros((n_out, self.features), np.float32)
         layout = self._layout(in_dim)
-        off = _check_offsets_arg(offsets, rows, self.pool == "sum")
+        off = _check_offsets_arg(offsets, rows, self.pool is not None)
         xd, x_dev = _prep_x(x)
         off = _device_offsets(off)
         sets = 0 if off is None else off.shape[0] - 1
@@ -509,7 +547,7 @@ class ConditionTrainer:
 
     Not provided: eval-mode input gradients (an eval forward leaves nothing
     pending), data parallelism, graph capture, saving the optimiser state,
-    pooling other than the sum."""
+    mean pooling inside the network (:func:`segment_mean` is the reduction alone)."""
 
     def __init__(self, net: ConditionNet, variables: Dict[str, Any], in_dim: int, rows_max: int,
                  sets_max: Optional[int] = None, optimizer=None):
