@@ -849,6 +849,44 @@ int zf_condnet_destroy(zf_condnet_t* handle);
 int zf_condnet_forward(zf_condnet_t* handle, const float* x, int64_t rows, const int64_t* off, int64_t sets,
                        int train, int update_stats, uint64_t seed, float* c_out, void* stream);
 
+/* Data-parallel conditioning networks: one handle per GPU, each holding
+ * whole sets of every global pass (a set lives on one rank).  The rules are
+ * zf_trainer_set_comm's: NULL / world 1 is a single device (the default),
+ * ZF_EINVAL for a bad rank or world and for a world above 1 without
+ * allgather, ZF_ENOTSUP above 64 ranks; the handle allocates the gather
+ * buffer, world x max(blob floats, 256) doubles.  A pending pass is dropped.
+ * Under a communicator at most three all-gathers of the ranks' fp64 subtree
+ * roots run per step, each combined by the top of the leaf tree
+ * (zf_reduce.h): BatchNorm's batch sums in a train-mode forward, its reverse
+ * sums in zf_condnet_backward_input (a network with BatchNorm only), and the
+ * gradient at the end of either reverse entry — one for a network without
+ * BatchNorm.  Sum and max pooling, the tie counts and dropout are per set or
+ * per element: nothing is exchanged for them.  Every rank gets the same
+ * gradient, statistics and (after zf_condnet_apply_gradient) parameters and
+ * optimiser state, bit for bit, for any split of whole sets; R ranks, R a
+ * power of two, with global_rows / R element rows each and global_rows a
+ * multiple of the leaf count, get the bits one device gets on the
+ * concatenated batch. */
+int zf_condnet_set_comm(zf_condnet_t* handle, const zf_comm_desc* comm);
+
+/* zf_condnet_forward on this rank's `rows` element rows of a global pass of
+ * global_rows rows, of which this rank's first is global row row_base: x,
+ * off (offsets local to x) and sets are this rank's own, c_out is (sets,
+ * out_dim) for this rank's sets ((rows, out_dim) with ZF_POOL_NONE).  The
+ * BatchNorm statistics are those of all global_rows rows, the dropout mask is
+ * keep(row_base + i, f), and global_rows picks the GEMM forms and the leaf
+ * layouts, so a shard runs the tile form of the one-device pass.
+ * zf_condnet_forward is the view with global_rows = rows, row_base = 0.
+ * The reverse entries read global_rows and row_base from the pending pass;
+ * their grad_out and the kept gradient are the global gradient, identical on
+ * every rank, while gc and gx_out hold this rank's rows.  Every rank must
+ * make the same calls in the same order.  ZF_EINVAL with nothing enqueued, on
+ * top of zf_condnet_forward's: global_rows < rows, row_base < 0, row_base +
+ * rows > global_rows, or world 1 and global_rows != rows. */
+int zf_condnet_forward_shard(zf_condnet_t* handle, const float* x, int64_t rows, int64_t global_rows,
+                             int64_t row_base, const int64_t* off, int64_t sets, int train, int update_stats,
+                             uint64_t seed, float* c_out, void* stream);
+
 /* Replaces jax.grad(loss_fn_2) for phi's parameters: gc (device, the shape of
  * the pending forward's c_out) = d loss / d c, e.g. the gc of
  * zf_trainer_step_cond_shard, of zf_trainer_sample_backward or of
@@ -891,11 +929,26 @@ int zf_condnet_apply_gradient(zf_condnet_t* handle, const float* grad, void* str
 int zf_condnet_set_optim_chain(zf_condnet_t* handle, const zf_optim_chain* chain,
                                const unsigned char* decay_mask);
 
-/* Copy the blob (parameters + statistics) out / in.  These two synchronise
- * with the host; no other zf_condnet_* or zf_segment_* entry does, and none
- * captures a graph or communicates. */
+/* Copy the blob (parameters + statistics) out / in.  These two, the four
+ * optimiser-state entries below, zf_condnet_set_optim_chain and a
+ * zf_condnet_set_comm that grows the gather buffer synchronise with the
+ * host; no other zf_condnet_* or zf_segment_* entry does.  None captures a
+ * graph.  Under a communicator of more than one rank
+ * zf_condnet_forward(_shard) in train mode with BatchNorm,
+ * zf_condnet_backward and zf_condnet_backward_input communicate
+ * (zf_condnet_set_comm); no other entry does. */
 int zf_condnet_get_blob(zf_condnet_t* handle, float* blob_host);
 int zf_condnet_set_blob(zf_condnet_t* handle, const float* blob_host);
+
+/* The optimiser's state, as zf_trainer_get_opt_slot / _set_opt_slot /
+ * _get_opt_scalars / _set_opt_count give and take the trainer's: the same
+ * arguments and errors; a handle's optimiser is always a chain (the (n)adamw
+ * of zf_condnet_create keeps two slots, mu and nu).  With the blob it is all
+ * a run needs to resume.  They synchronise. */
+int zf_condnet_get_opt_slot(zf_condnet_t* handle, int slot, float* host_floats);
+int zf_condnet_set_opt_slot(zf_condnet_t* handle, int slot, const float* host_floats);
+int zf_condnet_get_opt_scalars(zf_condnet_t* handle, int64_t* count, double* learning_rate, double* grad_norm);
+int zf_condnet_set_opt_count(zf_condnet_t* handle, int64_t count);
 
 /* ------------------------------------------------------------------------ */
 /* RCCL (over xGMI) — the NLL all-reduce of data-parallel log_prob and the  */

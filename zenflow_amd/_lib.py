@@ -235,6 +235,12 @@ SIGNATURES = {
     "zf_condnet_set_optim_chain": (_int, [_vp, _vp, _vp]),
     "zf_condnet_get_blob": (_int, [_vp, _vp]),
     "zf_condnet_set_blob": (_int, [_vp, _vp]),
+    "zf_condnet_set_comm": (_int, [_vp, _vp]),
+    "zf_condnet_forward_shard": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _int, _int, _u64, _vp, _vp]),
+    "zf_condnet_get_opt_slot": (_int, [_vp, _int, _vp]),
+    "zf_condnet_set_opt_slot": (_int, [_vp, _int, _vp]),
+    "zf_condnet_get_opt_scalars": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "zf_condnet_set_opt_count": (_int, [_vp, _i64]),
     "zf_latent_sample": (_int, [_int, _dbl, _u64, _vp, _i64, _int, _vp]),
     "zf_flow_set_bn_stats": (_int, [_vp, _int, _vp, _vp]),
     "zf_flow_set_sb_stats": (_int, [_vp, _int, _vp, _vp]),

@@ -10,6 +10,13 @@
 // zf_train_kernels.h, zf_optim.h): this unit instantiates its own copies of
 // those kernels, the trainer's code object is untouched.  New here: the
 // segmented reduction over ragged sets, its reverse, the repeat, and dropout.
+//
+// Data parallelism (zf_condnet_set_comm, zf_condnet_forward_shard): a rank
+// holds whole sets, B of the global pass's Bg element rows from row_base on.
+// Every leaf layout and GEMM form follows Bg, the ranks' fp64 subtree roots are
+// all-gathered and combined by the top of the leaf tree (cn_combine; the
+// gradient close), as the trainer does; pooling is per set and exchanges
+// nothing; the dropout mask is indexed by the global row.
 #include "zf_gemm.h"
 #include "zf_internal.h"
 #include "zf_optim.h"
@@ -31,7 +38,8 @@ constexpr int64_t kSegMaxRows = (1ll << 31) - 1;  // the row -> set index is int
 constexpr int kPlanThreads = 1024;
 
 // The dropout rule of include/zenflow_amd.h: d = keep(i, f) ? v / (1 - rate) : 0.
-// keep_prob = (float)1 - rate is formed once on the host.
+// keep_prob = (float)1 - rate is formed once on the host.  i is the row of the
+// global pass: the kernels add row_base (0 on one device and in zf_segment_*).
 template <bool DROP>
 __device__ __forceinline__ float drop_apply(float v, unsigned long long seed, long long i, int f, float rate,
                                             float keep_prob) {
@@ -123,11 +131,12 @@ __global__ __launch_bounds__(256) void seg_chunk_sum_kernel(const float* __restr
                                                             const long long* __restrict__ o,
                                                             const long long* __restrict__ cb, float rate,
                                                             float keep_prob, unsigned long long seed,
-                                                            float* __restrict__ part, float* __restrict__ out,
-                                                            int* __restrict__ set_index) {
+                                                            long long row_base, float* __restrict__ part,
+                                                            float* __restrict__ out, int* __restrict__ set_index) {
 #pragma clang fp contract(off)
   __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  // (the wave's number as a scalar: the chunk, its set, its first row and its mask row then live in SGPRs)
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long long c = (long long)blockIdx.x * 4 + w;
   const bool live = c < cb[S];
   const int R = 64 / F, j = lane / F, f = lane - j * F;
@@ -140,15 +149,16 @@ __global__ __launch_bounds__(256) void seg_chunk_sum_kernel(const float* __restr
     if (j < R) {
       const long long r0 = o[s] + (c - cb[s]) * kSegChunk;  // first row of the chunk
       const int len = (int)min((long long)kSegChunk, o[s + 1] - r0);
+      const long long d0 = r0 + row_base;  // its row in the dropout mask
       int r = j;
       for (; r + 7 * R < len; r += 8 * R) {
         float v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = h[(r0 + r + u * R) * F + f];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) acc = acc + drop_apply<DROP>(v[u], seed, r0 + r + u * R, f, rate, keep_prob);
+        for (int u = 0; u < 8; ++u) acc = acc + drop_apply<DROP>(v[u], seed, d0 + r + u * R, f, rate, keep_prob);
       }
-      for (; r < len; r += R) acc = acc + drop_apply<DROP>(h[(r0 + r) * F + f], seed, r0 + r, f, rate, keep_prob);
+      for (; r < len; r += R) acc = acc + drop_apply<DROP>(h[(r0 + r) * F + f], seed, d0 + r, f, rate, keep_prob);
       if (set_index && f == 0)
         for (int q = j; q < len; q += R) set_index[r0 + q] = (int)s;
     }
@@ -168,14 +178,14 @@ __global__ __launch_bounds__(256) void seg_chunk_sum_kernel(const float* __restr
 template <bool DROP>
 __global__ void seg_bcast_kernel(const float* __restrict__ gc, const int* __restrict__ idx, long long rows, int F,
                                  long long S, float rate, float keep_prob, unsigned long long seed,
-                                 float* __restrict__ g) {
+                                 long long row_base, float* __restrict__ g) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= rows * F) return;
   const long long i = t / F;
   const int f = (int)(t - i * F);
   const long long s = idx ? (long long)idx[i] : i;
   const float v = (s >= 0 && s < S) ? gc[s * F + f] : 0.f;
-  g[t] = drop_apply<DROP>(v, seed, i, f, rate, keep_prob);
+  g[t] = drop_apply<DROP>(v, seed, i + row_base, f, rate, keep_prob);
 }
 
 // ---- the repeat: out[i, :] = c[set(i), :] from the clamped offsets ------------------
@@ -238,11 +248,12 @@ __global__ __launch_bounds__(256) void seg_chunk_max_kernel(const float* __restr
                                                             const long long* __restrict__ o,
                                                             const long long* __restrict__ cb, float rate,
                                                             float keep_prob, unsigned long long seed,
-                                                            float* __restrict__ part, float* __restrict__ out,
-                                                            int* __restrict__ set_index) {
+                                                            long long row_base, float* __restrict__ part,
+                                                            float* __restrict__ out, int* __restrict__ set_index) {
 #pragma clang fp contract(off)
   __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  // (the wave's number as a scalar: the chunk, its set, its first row and its mask row then live in SGPRs)
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long long c = (long long)blockIdx.x * 4 + w;
   const bool live = c < cb[S];
   const int R = 64 / F, j = lane / F, f = lane - j * F;
@@ -255,6 +266,7 @@ __global__ __launch_bounds__(256) void seg_chunk_max_kernel(const float* __restr
     if (j < R) {
       const long long r0 = o[s] + (c - cb[s]) * kSegChunk;  // first row of the chunk
       const int len = (int)min((long long)kSegChunk, o[s + 1] - r0);
+      const long long d0 = r0 + row_base;  // its row in the dropout mask
       int r = j;
       for (; r + 7 * R < len; r += 8 * R) {
         float v[8];
@@ -262,9 +274,9 @@ __global__ __launch_bounds__(256) void seg_chunk_max_kernel(const float* __restr
         for (int u = 0; u < 8; ++u) v[u] = h[(r0 + r + u * R) * F + f];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          acc = nan_max(acc, drop_apply<DROP>(v[u], seed, r0 + r + u * R, f, rate, keep_prob));
+          acc = nan_max(acc, drop_apply<DROP>(v[u], seed, d0 + r + u * R, f, rate, keep_prob));
       }
-      for (; r < len; r += R) acc = nan_max(acc, drop_apply<DROP>(h[(r0 + r) * F + f], seed, r0 + r, f, rate, keep_prob));
+      for (; r < len; r += R) acc = nan_max(acc, drop_apply<DROP>(h[(r0 + r) * F + f], seed, d0 + r, f, rate, keep_prob));
       if (set_index && f == 0)
         for (int q = j; q < len; q += R) set_index[r0 + q] = (int)s;
     }
@@ -288,8 +300,8 @@ __global__ __launch_bounds__(256) void seg_chunk_ties_kernel(const float* __rest
                                                              const long long* __restrict__ o,
                                                              const long long* __restrict__ cb, float rate,
                                                              float keep_prob, unsigned long long seed,
-                                                             const float* __restrict__ m, int* __restrict__ cpart,
-                                                             int* __restrict__ count) {
+                                                             long long row_base, const float* __restrict__ m,
+                                                             int* __restrict__ cpart, int* __restrict__ count) {
   __shared__ int red[4][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long c = (long long)blockIdx.x * 4 + w;
@@ -304,6 +316,7 @@ __global__ __launch_bounds__(256) void seg_chunk_ties_kernel(const float* __rest
     if (j < R) {
       const long long r0 = o[s] + (c - cb[s]) * kSegChunk;
       const int len = (int)min((long long)kSegChunk, o[s + 1] - r0);
+      const long long d0 = r0 + row_base;
       const float top = m[s * F + f];
       int r = j;
       for (; r + 7 * R < len; r += 8 * R) {
@@ -312,10 +325,10 @@ __global__ __launch_bounds__(256) void seg_chunk_ties_kernel(const float* __rest
         for (int u = 0; u < 8; ++u) v[u] = h[(r0 + r + u * R) * F + f];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          acc += is_tie(drop_apply<DROP>(v[u], seed, r0 + r + u * R, f, rate, keep_prob), top) ? 1 : 0;
+          acc += is_tie(drop_apply<DROP>(v[u], seed, d0 + r + u * R, f, rate, keep_prob), top) ? 1 : 0;
       }
       for (; r < len; r += R)
-        acc += is_tie(drop_apply<DROP>(h[(r0 + r) * F + f], seed, r0 + r, f, rate, keep_prob), top) ? 1 : 0;
+        acc += is_tie(drop_apply<DROP>(h[(r0 + r) * F + f], seed, d0 + r, f, rate, keep_prob), top) ? 1 : 0;
     }
   }
   red[w][lane] = acc;
@@ -371,8 +384,9 @@ __global__ void seg_mean_finish_kernel(float* __restrict__ out, int F, long long
 template <bool DROP, bool MAX>
 __global__ void seg_pool_bcast_kernel(const float* __restrict__ gc, const int* __restrict__ idx, long long rows,
                                       int F, long long S, float rate, float keep_prob, unsigned long long seed,
-                                      const float* __restrict__ h, const float* __restrict__ m,
-                                      const int* __restrict__ count, float* __restrict__ g) {
+                                      long long row_base, const float* __restrict__ h,
+                                      const float* __restrict__ m, const int* __restrict__ count,
+                                      float* __restrict__ g) {
 #pragma clang fp contract(off)
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= rows * F) return;
@@ -380,7 +394,7 @@ __global__ void seg_pool_bcast_kernel(const float* __restrict__ gc, const int* _
   const int f = (int)(t - i * F);
   const long long s = idx[i];
   float v = 0.f;
-  const bool keep = drop_keep<DROP>(seed, i, f, rate);
+  const bool keep = drop_keep<DROP>(seed, i + row_base, f, rate);
   if (s >= 0 && s < S) {
     const int n = count[s * F + f];
     bool on = n > 0;
@@ -428,8 +442,10 @@ int seg_check(const void* a, const void* b, const void* c, long long rows, int F
 }
 
 // mx: the levels of the max (seg_chunk_max_kernel) over the same plan, workspace and grids.
+// row_base: row 0 of h in the dropout mask's numbering (a data-parallel shard's first global row; 0 otherwise).
 int seg_reduce_launch(const float* h, long long rows, int F, const long long* off, long long S, float rate,
-                      unsigned long long seed, float* out, int* set_index, void* ws, bool mx, hipStream_t st) {
+                      unsigned long long seed, long long row_base, float* out, int* set_index, void* ws, bool mx,
+                      hipStream_t st) {
   if (set_index) ZF_TRY_HIP(hipMemsetAsync(set_index, 0xff, (size_t)rows * sizeof(int), st));  // -1: in no set
   if (S == 0) return ZF_OK;
   ZF_TRY_HIP(hipMemsetAsync(out, 0, (size_t)S * F * sizeof(float), st));  // empty sets
@@ -451,7 +467,7 @@ int seg_reduce_launch(const float* h, long long rows, int F, const long long* of
     auto* const kernel = mx ? (drop ? seg_chunk_max_kernel<true> : seg_chunk_max_kernel<false>)
                             : (drop ? seg_chunk_sum_kernel<true> : seg_chunk_sum_kernel<false>);
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, in, F, S, (const long long*)o, (const long long*)cb, rate, kp,
-                       seed, dst, out, k == 0 ? set_index : nullptr);
+                       seed, row_base, dst, out, k == 0 ? set_index : nullptr);
     ZF_CHECK_LAUNCH(mx ? "seg_chunk_max_kernel" : "seg_chunk_sum_kernel");
     in = part;
     in_rows = chunks;
@@ -463,19 +479,19 @@ int seg_reduce_launch(const float* h, long long rows, int F, const long long* of
 
 int seg_sum_launch(const float* h, long long rows, int F, const long long* off, long long S, float rate,
                    unsigned long long seed, float* out, int* set_index, void* ws, hipStream_t st) {
-  return seg_reduce_launch(h, rows, F, off, S, rate, seed, out, set_index, ws, false, st);
+  return seg_reduce_launch(h, rows, F, off, S, rate, seed, 0, out, set_index, ws, false, st);
 }
 
 int seg_bcast_launch(const float* gc, const int* idx, long long rows, int F, long long S, float rate,
-                     unsigned long long seed, float* g, hipStream_t st) {
+                     unsigned long long seed, long long row_base, float* g, hipStream_t st) {
   if (rows == 0) return ZF_OK;
   const float kp = 1.0f - rate;
   if (rate > 0.f)
     hipLaunchKernelGGL(seg_bcast_kernel<true>, dim3(blocks_for(rows * F)), dim3(256), 0, st, gc, idx, rows, F, S, rate,
-                       kp, seed, g);
+                       kp, seed, row_base, g);
   else
     hipLaunchKernelGGL(seg_bcast_kernel<false>, dim3(blocks_for(rows * F)), dim3(256), 0, st, gc, idx, rows, F, S,
-                       rate, kp, seed, g);
+                       rate, kp, seed, row_base, g);
   ZF_CHECK_LAUNCH("seg_bcast_kernel");
   return ZF_OK;
 }
@@ -511,8 +527,10 @@ inline long long seg_pool_ws_bytes(long long rows, long long S, int F, int pool)
 // max's levels, then (with count) the two tie-count passes over the first
 // level's plan, which the levels leave in the workspace.
 int seg_pool_launch(const float* h, long long rows, int F, const long long* off, long long S, int pool, float rate,
-                    unsigned long long seed, float* out, int* set_index, int* count, void* ws, hipStream_t st) {
-  const int rc = seg_reduce_launch(h, rows, F, off, S, rate, seed, out, set_index, ws, pool == ZF_POOL_MAX, st);
+                    unsigned long long seed, long long row_base, float* out, int* set_index, int* count, void* ws,
+                    hipStream_t st) {
+  const int rc =
+      seg_reduce_launch(h, rows, F, off, S, rate, seed, row_base, out, set_index, ws, pool == ZF_POOL_MAX, st);
   if (rc || S == 0 || pool == ZF_POOL_SUM) return rc;
   const long long* o = (const long long*)ws;
   const long long* cb = o + (S + 1);
@@ -527,10 +545,10 @@ int seg_pool_launch(const float* h, long long rows, int F, const long long* off,
   const float kp = 1.0f - rate;
   const dim3 grid((unsigned)((seg_max_chunks(rows, S) + 3) / 4));
   if (rate > 0.f)
-    hipLaunchKernelGGL(seg_chunk_ties_kernel<true>, grid, dim3(256), 0, st, h, F, S, o, cb, rate, kp, seed,
+    hipLaunchKernelGGL(seg_chunk_ties_kernel<true>, grid, dim3(256), 0, st, h, F, S, o, cb, rate, kp, seed, row_base,
                        (const float*)out, cpart, count);
   else
-    hipLaunchKernelGGL(seg_chunk_ties_kernel<false>, grid, dim3(256), 0, st, h, F, S, o, cb, rate, kp, seed,
+    hipLaunchKernelGGL(seg_chunk_ties_kernel<false>, grid, dim3(256), 0, st, h, F, S, o, cb, rate, kp, seed, row_base,
                        (const float*)out, cpart, count);
   ZF_CHECK_LAUNCH("seg_chunk_ties_kernel");
   hipLaunchKernelGGL(seg_ties_sum_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, (const int*)cpart, F, S, cb,
@@ -540,16 +558,16 @@ int seg_pool_launch(const float* h, long long rows, int F, const long long* off,
 }
 
 int seg_pool_bcast_launch(const float* gc, const int* idx, long long rows, int F, long long S, int pool, float rate,
-                          unsigned long long seed, const float* h, const float* m, const int* count, float* g,
-                          hipStream_t st) {
-  if (pool == ZF_POOL_SUM) return seg_bcast_launch(gc, idx, rows, F, S, rate, seed, g, st);
+                          unsigned long long seed, long long row_base, const float* h, const float* m,
+                          const int* count, float* g, hipStream_t st) {
+  if (pool == ZF_POOL_SUM) return seg_bcast_launch(gc, idx, rows, F, S, rate, seed, row_base, g, st);
   if (rows == 0) return ZF_OK;
   const float kp = 1.0f - rate;
   const bool mx = pool == ZF_POOL_MAX, drop = rate > 0.f;
   auto* const kernel = mx ? (drop ? seg_pool_bcast_kernel<true, true> : seg_pool_bcast_kernel<false, true>)
                           : (drop ? seg_pool_bcast_kernel<true, false> : seg_pool_bcast_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3(blocks_for(rows * F)), dim3(256), 0, st, gc, idx, rows, F, S, rate, kp, seed, h, m,
-                     count, g);
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(rows * F)), dim3(256), 0, st, gc, idx, rows, F, S, rate, kp, seed,
+                     row_base, h, m, count, g);
   ZF_CHECK_LAUNCH("seg_pool_bcast_kernel");
   return ZF_OK;
 }
@@ -591,7 +609,12 @@ struct zf_condnet {
   // the pending train-mode pass
   bool pending = false;
   int64_t pend_rows = 0, pend_sets = 0;
+  int64_t pend_global = 0, pend_base = 0;  // the global pass's rows, this rank's first row in it
   uint64_t pend_seed = 0;
+  // data parallelism (zf_condnet_set_comm): world 1 is one device
+  zf_comm_desc comm{0, 1, nullptr, nullptr};
+  double* d_gath = nullptr;  // [world][max(nat_floats, 256)] the ranks' fp64 roots
+  int64_t gath_bytes = 0;
   // optimiser chain
   zf::ChainPlan plan;
   std::vector<void*> opt_bufs;
@@ -717,10 +740,23 @@ zf_optim_chain adamw_chain(const zf_optim_desc& o) {
 inline int layer_out(const zf_condnet* h, int l) { return l == h->L ? h->F : h->desc.hidden[l]; }
 inline int layer_in(const zf_condnet* h, int l) { return l == 0 ? h->in : h->desc.hidden[l - 1]; }
 
-// BatchNorm of the pass's rows: train mode on their own statistics (the
-// trainer's multi-launch path: leaf sums in row order, the fp64 leaf tree,
-// bn_stats_kernel, bn_apply_kernel), eval mode on the stored ones.
-int cn_batchnorm(zf_condnet* h, const float* x, int B, int train, int update_stats, hipStream_t st) {
+// Data parallelism, as the trainer's dp_combine: this rank's tree roots (n
+// doubles, in place) -> the global ones: all-gather every rank's roots,
+// combine them by the top of the leaf tree.  Nothing to do on one device.
+int cn_combine(zf_condnet* h, double* roots, long long n, hipStream_t st) {
+  const int W = h->comm.world;
+  if (W <= 1) return ZF_OK;
+  if ((int64_t)n * (int64_t)sizeof(double) * W > h->gath_bytes) return einval("all-gather buffer too small");
+  const int rc = h->comm.allgather(h->comm.ctx, roots, h->d_gath, (size_t)n * sizeof(double), st);
+  if (rc) return rc;
+  return launch_tree_cols((const double*)h->d_gath, W, n, roots, st);
+}
+
+// BatchNorm of the pass's B rows, this rank's shard of Bg: train mode on the
+// statistics of all Bg rows (the trainer's multi-launch path: leaf sums in row
+// order, the fp64 leaf tree, the ranks' roots combined, bn_stats_kernel,
+// bn_apply_kernel), eval mode on the stored ones.
+int cn_batchnorm(zf_condnet* h, const float* x, int B, long long Bg, int train, int update_stats, hipStream_t st) {
   const int DC = h->in;
   float* bn = h->d_nat + h->desc.off_bn;  // [mean, var, scale, bias]
   if (!train) {
@@ -730,14 +766,15 @@ int cn_batchnorm(zf_condnet* h, const float* x, int B, int train, int update_sta
     ZF_CHECK_LAUNCH("bn_eval_fwd_kernel");
     return ZF_OK;
   }
-  const Leaves lbn = leaves_for(B, B, 1, kBnLeafCap);
+  const Leaves lbn = leaves_for(B, Bg, h->comm.world, kBnLeafCap);
   hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st, x,
                      (const float*)nullptr, B, DC, lbn.rows, lbn.n, h->d_leaf);
   ZF_CHECK_LAUNCH("leaf_colsums_kernel");
-  const int rc = launch_tree_cols(h->d_leaf, lbn.n, 2 * DC, h->d_roots, st, h->d_leaf2);
+  int rc = launch_tree_cols(h->d_leaf, lbn.n, 2 * DC, h->d_roots, st, h->d_leaf2);
   if (rc) return rc;
+  if ((rc = cn_combine(h, h->d_roots, 2 * DC, st))) return rc;
   hipLaunchKernelGGL(bn_stats_kernel, dim3(1), dim3(64), 0, st, (const double*)h->d_roots,
-                     (const double*)(h->d_roots + DC), (long long)B, DC, bn, h->d_mean, h->d_rstd, update_stats);
+                     (const double*)(h->d_roots + DC), Bg, DC, bn, h->d_mean, h->d_rstd, update_stats);
   ZF_CHECK_LAUNCH("bn_stats_kernel");
   hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, x,
                      (const float*)h->d_mean, (const float*)h->d_rstd, (const float*)(bn + 2 * DC),
@@ -747,14 +784,14 @@ int cn_batchnorm(zf_condnet* h, const float* x, int B, int train, int update_sta
 }
 
 // The Dense chain: `in` -> Z[l], H[l] = act(Z[l]) -> out_last (B rows of F).
-// Eval mode keeps no pre-activations.
-int cn_dense_fwd(zf_condnet* h, const float* in, int B, int train, float* out_last, hipStream_t st) {
+// Eval mode keeps no pre-activations.  Bg picks the GEMM forms.
+int cn_dense_fwd(zf_condnet* h, const float* in, int B, long long Bg, int train, float* out_last, hipStream_t st) {
   const float* nat = h->d_nat;
   for (int l = 0; l <= h->L; ++l) {
     const bool last = l == h->L;
     const int in_w = layer_in(h, l), out_w = layer_out(h, l);
     float* C = last ? out_last : (train ? h->Z[l] : nullptr);
-    const int rc = gemm(false, B, B, out_w, in_w, in, in_w, nat + h->desc.off_w[l], out_w, C, out_w, st, kEpiBias,
+    const int rc = gemm(false, Bg, B, out_w, in_w, in, in_w, nat + h->desc.off_w[l], out_w, C, out_w, st, kEpiBias,
                         nat + h->desc.off_b[l], last ? nullptr : h->H[l], nullptr, h->desc.act, h->d_split,
                         kSplitFloats);
     if (rc) return rc;
@@ -763,14 +800,15 @@ int cn_dense_fwd(zf_condnet* h, const float* in, int B, int train, float* out_la
   return ZF_OK;
 }
 
-int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long long S, int train, int update_stats,
-               unsigned long long seed, float* c_out, hipStream_t st) {
+// The pass on this rank's B rows, rows [row_base, row_base + B) of a global pass of Bg (one device: B, 0).
+int cn_forward(zf_condnet* h, const float* x, int B, long long Bg, long long row_base, const long long* off,
+               long long S, int train, int update_stats, unsigned long long seed, float* c_out, hipStream_t st) {
   const bool pool = h->desc.pool != ZF_POOL_NONE;
   const float rate = train ? h->desc.dropout : 0.f;
   int rc;
   const float* in0 = x;
   if (h->desc.batch_norm) {
-    if ((rc = cn_batchnorm(h, x, B, train, update_stats, st))) return rc;
+    if ((rc = cn_batchnorm(h, x, B, Bg, train, update_stats, st))) return rc;
     in0 = h->d_ubn;
   } else if (train) {  // layer 0's weight gradient reads its input after the caller's x may be gone
     ZF_TRY_HIP(hipMemcpyAsync(h->d_x, x, (size_t)B * h->in * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -778,16 +816,16 @@ int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long 
   }
   // per-row output without dropout: the last Dense writes c_out itself
   float* hl = (!pool && rate == 0.f) ? c_out : h->d_h;
-  if ((rc = cn_dense_fwd(h, in0, B, train, hl, st))) return rc;
+  if ((rc = cn_dense_fwd(h, in0, B, Bg, train, hl, st))) return rc;
   if (pool) {
-    rc = seg_pool_launch(hl, B, h->F, off, S, h->desc.pool, rate, seed, c_out, train ? h->d_set : nullptr,
+    rc = seg_pool_launch(hl, B, h->F, off, S, h->desc.pool, rate, seed, row_base, c_out, train ? h->d_set : nullptr,
                          train ? h->d_cnt : nullptr, h->d_segws, st);
     if (rc || !train || h->desc.pool != ZF_POOL_MAX) return rc;
     // the reverse reads the maxima after the caller's c_out may be gone
     ZF_TRY_HIP(hipMemcpyAsync(h->d_pool, c_out, (size_t)S * h->F * sizeof(float), hipMemcpyDeviceToDevice, st));
     return ZF_OK;
   }
-  if (rate > 0.f) return seg_bcast_launch(hl, nullptr, B, h->F, B, rate, seed, c_out, st);
+  if (rate > 0.f) return seg_bcast_launch(hl, nullptr, B, h->F, B, rate, seed, row_base, c_out, st);
   return ZF_OK;
 }
 
@@ -799,18 +837,19 @@ int cn_forward(zf_condnet* h, const float* x, int B, const long long* off, long 
 // GEMM (without BatchNorm, straight into gx_out) or BatchNorm's train-mode
 // reverse on the column sums the scale and bias gradients reduce anyway.
 int cn_backward(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, hipStream_t st) {
-  const int B = (int)h->pend_rows;
+  const int B = (int)h->pend_rows, W = h->comm.world;
+  const long long Bg = h->pend_global, row_base = h->pend_base;
   const bool pool = h->desc.pool != ZF_POOL_NONE;
   const float rate = h->desc.dropout;
   int rc;
   const float* gout = gc;
   if (pool) {
-    rc = seg_pool_bcast_launch(gc, h->d_set, B, h->F, h->pend_sets, h->desc.pool, rate, h->pend_seed, h->d_h,
-                               h->d_pool, h->d_cnt, h->d_gl, st);
+    rc = seg_pool_bcast_launch(gc, h->d_set, B, h->F, h->pend_sets, h->desc.pool, rate, h->pend_seed, row_base,
+                               h->d_h, h->d_pool, h->d_cnt, h->d_gl, st);
     if (rc) return rc;
     gout = h->d_gl;
   } else if (rate > 0.f) {
-    if ((rc = seg_bcast_launch(gc, nullptr, B, h->F, B, rate, h->pend_seed, h->d_gl, st))) return rc;
+    if ((rc = seg_bcast_launch(gc, nullptr, B, h->F, B, rate, h->pend_seed, row_base, h->d_gl, st))) return rc;
     gout = h->d_gl;
   }
   WgradQueue wq;
@@ -822,13 +861,13 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, 
     const float* hin = l == 0 ? (h->desc.batch_norm ? h->d_ubn : h->d_x) : h->H[l - 1];
     const int cap =
         pow2floor(std::min<int64_t>(kLeafCap, std::max<int64_t>(1, kWsFloats / ((int64_t)(in_w + 1) * out_w))));
-    rc = wgrad_deferred(wq, in_w, out_w, B, leaves_for(B, B, 1, cap), hin, gout, h->d_g64 + h->desc.off_w[l],
+    rc = wgrad_deferred(wq, in_w, out_w, B, leaves_for(B, Bg, W, cap), hin, gout, h->d_g64 + h->desc.off_w[l],
                         h->d_g64 + h->desc.off_b[l], h->d_ws, h->d_ws2, st);
     if (rc) return rc;
     if (l == 0 && !h->desc.batch_norm && !gx_out) break;  // d / d x is not asked for
     float* const gin = l == 0 ? (h->desc.batch_norm ? h->d_gu : gx_out) : (which ? h->d_gb : h->d_ga);
     if ((rc = wgrad_before_write(wq, gin, st))) return rc;  // a deferred dW GEMM still reads it
-    rc = gemm(true, B, B, in_w, out_w, gout, out_w, h->d_nat + h->desc.off_w[l], out_w, gin, in_w, st,
+    rc = gemm(true, Bg, B, in_w, out_w, gout, out_w, h->d_nat + h->desc.off_w[l], out_w, gin, in_w, st,
               l > 0 ? kEpiDSwish : kEpiNone, nullptr, nullptr, l > 0 ? h->Z[l - 1] : nullptr, h->desc.act, h->d_split,
               kSplitFloats);
     if (rc) return rc;
@@ -839,7 +878,7 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, 
   if (h->desc.batch_norm) {
     // scale / bias: the sums of gUbn * Uhat and gUbn over the rows
     const int DC = h->in;
-    const Leaves lbn = leaves_for(B, B, 1, kBnLeafCap);
+    const Leaves lbn = leaves_for(B, Bg, W, kBnLeafCap);
     double* gbn = h->d_g64 + h->desc.off_bn;
     hipLaunchKernelGGL(leaf_colsums_kernel, dim3(blocks_for((int64_t)lbn.n * DC)), dim3(256), 0, st,
                        (const float*)h->d_gu, (const float*)h->d_uhat, B, DC, lbn.rows, lbn.n, h->d_leaf);
@@ -848,17 +887,31 @@ int cn_backward(zf_condnet* h, const float* gc, float* grad_out, float* gx_out, 
     ZF_TRY_HIP(hipMemcpyAsync(gbn + 3 * DC, h->d_roots, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
     ZF_TRY_HIP(hipMemcpyAsync(gbn + 2 * DC, h->d_roots + DC, DC * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (gx_out) {
-      // d / d x: the batch terms are those two sums over all B rows of the pass (padding rows are in the statistics)
+      // d / d x: the batch terms are those two sums over all Bg rows of the pass (padding rows are in the
+      // statistics).  The scale / bias slots above hold this rank's roots (the gradient close adds the ranks');
+      // the reverse formula takes the global ones.
+      if ((rc = cn_combine(h, h->d_roots, 2 * DC, st))) return rc;
       hipLaunchKernelGGL(bn_bwd_kernel, dim3(blocks_for((int64_t)B * DC)), dim3(256), 0, st, (const float*)h->d_gu,
                          (const float*)h->d_uhat, (const float*)(h->d_nat + h->desc.off_bn + 2 * DC),
                          (const float*)h->d_rstd, (const double*)h->d_roots, (const double*)(h->d_roots + DC), gx_out,
-                         B, (long long)B, DC);
+                         B, Bg, DC);
       ZF_CHECK_LAUNCH("bn_bwd_kernel");
     }
   }
-  hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(h->nat_floats)), dim3(256), 0, st,
-                     (const double*)h->d_g64, (long long)h->nat_floats, h->d_grad, (float*)nullptr, 0.f, 0.f);
-  ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
+  // the gradient close, as the trainer's close_gradient: every rank's fp64 share, the tree over the ranks, fp32
+  if (W > 1) {
+    rc = h->comm.allgather(h->comm.ctx, h->d_g64, h->d_gath, (size_t)h->nat_floats * sizeof(double), st);
+    if (rc) return rc;
+#define ZF_L(NM) hipLaunchKernelGGL((tree_cols_cast_kernel<NM>), dim3(blocks_for(h->nat_floats)), dim3(256), 0, st, \
+                                    (const double*)h->d_gath, W, (long long)h->nat_floats, h->d_grad)
+    ZF_NMAX_DISPATCH(W, ZF_L);
+#undef ZF_L
+    ZF_CHECK_LAUNCH("tree_cols_cast_kernel");
+  } else {
+    hipLaunchKernelGGL(cast_f64_f32_kernel, dim3(blocks_for(h->nat_floats)), dim3(256), 0, st,
+                       (const double*)h->d_g64, (long long)h->nat_floats, h->d_grad, (float*)nullptr, 0.f, 0.f);
+    ZF_CHECK_LAUNCH("cast_f64_f32_kernel");
+  }
   h->have_grad = true;
   if (grad_out && grad_out != h->d_grad)
     ZF_TRY_HIP(hipMemcpyAsync(grad_out, h->d_grad, (size_t)h->nat_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -898,7 +951,7 @@ int zf_segment_bcast(const float* gc, const int32_t* set_index, int64_t rows, in
                      uint64_t seed, float* g_h, void* stream) {
   const int rc = zf::seg_check(gc, set_index, g_h, rows, F, sets, rate);
   if (rc) return rc;
-  return zf::seg_bcast_launch(gc, set_index, rows, F, sets, rate, seed, g_h, (hipStream_t)stream);
+  return zf::seg_bcast_launch(gc, set_index, rows, F, sets, rate, seed, 0, g_h, (hipStream_t)stream);
 }
 
 int64_t zf_segment_pool_workspace_bytes(int64_t rows, int64_t sets, int F, int pool) {
@@ -912,7 +965,7 @@ int zf_segment_pool(const float* h, int64_t rows, int F, const int64_t* off, int
   const int rc = zf::seg_check(h, off, out, rows, F, sets, rate);
   if (rc) return rc;
   if (!workspace) return zf::einval("segment: NULL workspace");
-  return zf::seg_pool_launch(h, rows, F, (const long long*)off, sets, pool, rate, seed, out, set_index, count,
+  return zf::seg_pool_launch(h, rows, F, (const long long*)off, sets, pool, rate, seed, 0, out, set_index, count,
                              workspace, (hipStream_t)stream);
 }
 
@@ -924,7 +977,7 @@ int zf_segment_pool_bcast(const float* gc, const int32_t* set_index, int64_t row
   if (rc) return rc;
   if (pool != ZF_POOL_SUM && !count) return zf::einval("segment: NULL count");
   if (pool == ZF_POOL_MAX && (!h || !out)) return zf::einval("segment: the max's reverse needs h and out");
-  return zf::seg_pool_bcast_launch(gc, set_index, rows, F, sets, pool, rate, seed, h, out, count, g_h,
+  return zf::seg_pool_bcast_launch(gc, set_index, rows, F, sets, pool, rate, seed, 0, h, out, count, g_h,
                                    (hipStream_t)stream);
 }
 
@@ -1032,17 +1085,51 @@ int zf_condnet_destroy(zf_condnet_t* h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->bufs) (void)hipFree(p);
   zf::cn_free_chain(h);
+  if (h->d_gath) (void)hipFree(h->d_gath);
   delete h;
+  return ZF_OK;
+}
+
+int zf_condnet_set_comm(zf_condnet_t* h, const zf_comm_desc* comm) {
+  if (!h) return zf::einval("condnet is NULL");
+  zf_comm_desc c{0, 1, nullptr, nullptr};
+  if (comm) c = *comm;
+  if (c.world < 1 || c.rank < 0 || c.rank >= c.world) return zf::einval("bad rank %d / world %d", c.rank, c.world);
+  if (c.world > zf::kMaxLeaves) return zf::enotsup("condnet: more than 64 ranks");
+  if (c.world > 1 && !c.allgather) return zf::einval("communicator without allgather");
+  // the gather buffer only grows (largest exchange: the fp64 gradient of every rank)
+  const int64_t need =
+      c.world > 1 ? std::max<int64_t>(h->nat_floats, 256) * (int64_t)sizeof(double) * c.world : 0;
+  if (need > h->gath_bytes) {
+    ZF_TRY_HIP(hipDeviceSynchronize());
+    if (h->d_gath) (void)hipFree(h->d_gath);
+    h->d_gath = nullptr;
+    h->gath_bytes = 0;
+    ZF_TRY_HIP(hipMalloc((void**)&h->d_gath, (size_t)need));
+    h->gath_bytes = need;
+  }
+  h->pending = false;  // a pending pass belongs to the layout it ran under
+  h->comm = c;
   return ZF_OK;
 }
 
 int zf_condnet_forward(zf_condnet_t* h, const float* x, int64_t rows, const int64_t* off, int64_t sets, int train,
                        int update_stats, uint64_t seed, float* c_out, void* stream) {
+  return zf_condnet_forward_shard(h, x, rows, rows, 0, off, sets, train, update_stats, seed, c_out, stream);
+}
+
+int zf_condnet_forward_shard(zf_condnet_t* h, const float* x, int64_t rows, int64_t global_rows, int64_t row_base,
+                             const int64_t* off, int64_t sets, int train, int update_stats, uint64_t seed,
+                             float* c_out, void* stream) {
   if (!h) return zf::einval("condnet is NULL");
   h->pending = false;
   if (!x || !c_out) return zf::einval("NULL argument");
   if (rows < 1 || rows > h->rows_max)
     return zf::einval("rows %lld outside [1, rows_max = %lld]", (long long)rows, (long long)h->rows_max);
+  if (global_rows < rows || row_base < 0 || row_base > global_rows - rows ||
+      (h->comm.world == 1 && global_rows != rows))
+    return zf::einval("global_rows %lld, row_base %lld vs rows %lld (world %d)", (long long)global_rows,
+                      (long long)row_base, (long long)rows, h->comm.world);
   const bool pool = h->desc.pool != ZF_POOL_NONE;
   if (pool) {
     if (!off) return zf::einval("a pooled network needs the sets' offsets");
@@ -1054,12 +1141,14 @@ int zf_condnet_forward(zf_condnet_t* h, const float* x, int64_t rows, const int6
   if (!train && update_stats) return zf::einval("update_stats needs train mode (eval mode reads the stored statistics)");
   int rc = train ? zf::cn_ensure_train(h) : ZF_OK;
   if (rc) return rc;
-  rc = zf::cn_forward(h, x, (int)rows, (const long long*)off, pool ? sets : 0, train ? 1 : 0,
-                                update_stats ? 1 : 0, seed, c_out, (hipStream_t)stream);
+  rc = zf::cn_forward(h, x, (int)rows, global_rows, row_base, (const long long*)off, pool ? sets : 0, train ? 1 : 0,
+                      update_stats ? 1 : 0, seed, c_out, (hipStream_t)stream);
   if (rc) return rc;
   if (train) {
     h->pending = true;
     h->pend_rows = rows;
+    h->pend_global = global_rows;
+    h->pend_base = row_base;
     h->pend_sets = pool ? sets : 0;
     h->pend_seed = seed;
   }
@@ -1098,6 +1187,55 @@ int zf_condnet_set_optim_chain(zf_condnet_t* h, const zf_optim_chain* chain, con
   if (rc) return rc;
   ZF_TRY_HIP(hipDeviceSynchronize());
   return zf::cn_install_chain(h, plan, decay_mask);
+}
+
+// The optimiser state, as zf_trainer_{get,set}_opt_*: a handle's optimiser is always a chain.
+static int cn_opt_slot_ptr(zf_condnet_t* h, int slot, float** p) {
+  if (!h) return zf::einval("condnet is NULL");
+  const int n = h->plan.n_slots;
+  if (slot < 0 || slot >= n) return zf::einval("optimiser slot %d outside [0, %d)", slot, n);
+  *p = h->plan.args.slot[slot];
+  return ZF_OK;
+}
+
+int zf_condnet_get_opt_slot(zf_condnet_t* h, int slot, float* host_floats) {
+  float* p = nullptr;
+  const int rc = cn_opt_slot_ptr(h, slot, &p);
+  if (rc) return rc;
+  if (!host_floats) return zf::einval("NULL argument");
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  ZF_TRY_HIP(hipMemcpy(host_floats, p, h->nat_floats * sizeof(float), hipMemcpyDeviceToHost));
+  return ZF_OK;
+}
+
+int zf_condnet_set_opt_slot(zf_condnet_t* h, int slot, const float* host_floats) {
+  float* p = nullptr;
+  const int rc = cn_opt_slot_ptr(h, slot, &p);
+  if (rc) return rc;
+  if (!host_floats) return zf::einval("NULL argument");
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  ZF_TRY_HIP(hipMemcpy(p, host_floats, h->nat_floats * sizeof(float), hipMemcpyHostToDevice));
+  return ZF_OK;
+}
+
+int zf_condnet_get_opt_scalars(zf_condnet_t* h, int64_t* count, double* learning_rate, double* grad_norm) {
+  if (!h) return zf::einval("condnet is NULL");
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  zf::OptScalars sc;
+  ZF_TRY_HIP(hipMemcpy(&sc, h->d_osc, sizeof(sc), hipMemcpyDeviceToHost));
+  if (count) *count = sc.count;
+  if (learning_rate) *learning_rate = sc.count > 0 ? (double)sc.lr : (double)__builtin_nanf("");  // no step yet
+  if (grad_norm) *grad_norm = sc.count > 0 ? sc.norm : (double)__builtin_nanf("");
+  return ZF_OK;
+}
+
+int zf_condnet_set_opt_count(zf_condnet_t* h, int64_t count) {
+  if (!h) return zf::einval("condnet is NULL");
+  if (count < 0 || count > 0x7fffffff) return zf::einval("optimiser count %lld outside [0, 2^31)", (long long)count);
+  ZF_TRY_HIP(hipDeviceSynchronize());
+  const long long c = count;
+  ZF_TRY_HIP(hipMemcpy(&h->d_osc->count, &c, sizeof(c), hipMemcpyHostToDevice));
+  return ZF_OK;
 }
 
 int zf_condnet_get_blob(zf_condnet_t* h, float* blob_host) {

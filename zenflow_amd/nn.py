@@ -56,7 +56,7 @@ from .module import Module, lecun_normal, scope_for
 from .optim import Chain
 
 __all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "clamp_offsets", "dropout_keep", "segment_max",
-           "segment_mean", "segment_repeat", "segment_sum"]
+           "segment_mean", "segment_repeat", "segment_sum", "shard_sets"]
 
 _U64 = (1 << 64) - 1
 _POOLS = {None: L.ZF_POOL_NONE, "sum": L.ZF_POOL_SUM, "max": L.ZF_POOL_MAX}
@@ -87,6 +87,23 @@ def clamp_offsets(offsets, rows: int) -> np.ndarray:
     [0, rows], then the running maximum (zf_segment_sum)."""
     a = np.clip(np.asarray(offsets, np.int64), 0, int(rows))
     return np.maximum.accumulate(a)
+
+
+def shard_sets(offsets, rank: int, world: int) -> Tuple[int, int, int, int]:
+    """``(s0, s1, r0, r1)``: the sets ``[s0, s1)`` and the element rows
+    ``[r0, r1) = [offsets[s0], offsets[s1])`` of ``rank`` when the S sets of
+    ``offsets`` (S + 1, validated with :func:`check_offsets`) are split
+    contiguously over ``world`` ranks as ``dist.shard_rows`` splits rows: a set
+    lives on one rank, and the flow's rows are the sets, so ``[s0, s1)`` is
+    also the flow trainer's shard.  The rank's own pass takes
+    ``offsets[s0:s1 + 1] - offsets[s0]`` with ``row_base=r0`` and
+    ``global_rows=offsets[-1]``.  With more ranks than sets the last ranks
+    get none (``s0 == s1``)."""
+    from .dist import shard_rows
+
+    off = check_offsets(offsets, np.iinfo(np.int64).max)
+    s0, s1 = shard_rows(off.size - 1, int(rank), int(world))
+    return s0, s1, int(off[s0]), int(off[s1])
 
 
 def dropout_keep(seed: int, rows, cols: int, rate: float) -> np.ndarray:
@@ -352,13 +369,16 @@ class _Handle:
     def pooled(self) -> bool:
         return self.layout.desc.pool != L.ZF_POOL_NONE
 
-    def forward(self, xd: DeviceArray, off: Optional[DeviceArray], train: bool, update_stats: bool, seed: int):
+    def forward(self, xd: DeviceArray, off: Optional[DeviceArray], train: bool, update_stats: bool, seed: int,
+                global_rows: Optional[int] = None, row_base: int = 0):
+        """``xd``: this rank's rows, from global row ``row_base`` on, of a pass of ``global_rows`` (None: its own) rows."""
         rows = xd.shape[0]
         sets = 0 if off is None else off.shape[0] - 1
         out = DeviceArray((sets if self.pooled else rows, self.layout.desc.out_dim))
-        check(L.load_library().zf_condnet_forward(
-            self.ptr, xd.ptr, rows, None if off is None else off.ptr, sets, 1 if train else 0,
-            1 if update_stats else 0, _seed64(seed), out.ptr, L.stream()), "zf_condnet_forward")
+        check(L.load_library().zf_condnet_forward_shard(
+            self.ptr, xd.ptr, rows, rows if global_rows is None else int(global_rows), int(row_base),
+            None if off is None else off.ptr, sets, 1 if train else 0, 1 if update_stats else 0, _seed64(seed),
+            out.ptr, L.stream()), "zf_condnet_forward_shard")
         return out
 
     def blob(self) -> np.ndarray:
@@ -545,12 +565,29 @@ class ConditionTrainer:
         yp = rt.forward(c)
         pt.step(rt.step(gy, input_grad=True))
 
+    ``comm``: data parallelism, as ``Trainer(comm=)`` takes it
+    (``dist.RcclCommunicator``, or ``dist.HostAllgather`` for ranks sharing a
+    GPU).  Every rank holds whole sets (:func:`shard_sets`) and calls
+    ``forward`` / ``backward`` / ``apply_gradient`` with its own element rows,
+    offsets and ``gc`` rows — under ``tr = Trainer(..., comm=comm)`` the ``gc``
+    of ``tr.step(Y[s0:s1], c, cond_grad=True)`` is just that.  BatchNorm's
+    batch sums (forward, and reverse when ``input_grad=True``) and the
+    gradient are exchanged as the ranks' fp64 tree roots: at most three
+    all-gathers a step, one for a network without BatchNorm.  Every rank ends
+    with the same gradient, parameters, statistics and optimiser state, bit
+    for bit, for any split of whole sets; R ranks (a power of two) with
+    ``global_rows / R`` element rows each, ``global_rows`` a multiple of the
+    leaf count, reproduce the bits of one device on the concatenated batch.
+
+    :meth:`opt_state` / :meth:`load_opt_state` with :meth:`variables` are all
+    a run needs to resume.
+
     Not provided: eval-mode input gradients (an eval forward leaves nothing
-    pending), data parallelism, graph capture, saving the optimiser state,
+    pending), splitting one set across ranks, graph capture,
     mean pooling inside the network (:func:`segment_mean` is the reduction alone)."""
 
     def __init__(self, net: ConditionNet, variables: Dict[str, Any], in_dim: int, rows_max: int,
-                 sets_max: Optional[int] = None, optimizer=None):
+                 sets_max: Optional[int] = None, optimizer=None, comm=None):
         from .train import DEFAULT_OPTIMIZER, Optimizer
 
         self.net = net
@@ -577,6 +614,12 @@ class ConditionTrainer:
                 "zf_condnet_set_optim_chain")
         self._pending: Optional[Tuple[int, bool, int]] = None  # (rows of c, device result?, rows of x)
         self._last_grad: Optional[DeviceArray] = None
+        self.comm = comm
+        self.rank, self.world = 0, 1
+        if comm is not None:
+            self._comm_desc = comm.trainer_comm_desc()  # kept alive: the C side holds its pointers
+            check(L.load_library().zf_condnet_set_comm(self._h.ptr, ct.byref(self._comm_desc)), "zf_condnet_set_comm")
+            self.rank, self.world = int(comm.rank), int(comm.world)
 
     @property
     def handle(self) -> int:
@@ -595,13 +638,32 @@ class ConditionTrainer:
             mask = mask(variables["params"])
         return np.ascontiguousarray(self.layout.to_blob({"params": mask}, cols=("params",), dtype=np.uint8))
 
-    def forward(self, x, offsets=None, *, train: bool = True, update_stats: Optional[bool] = None, seed: int = 0):
+    def _shard(self, rows: int, global_rows: Optional[int], row_base: Optional[int]) -> Tuple[int, int]:
+        """(global_rows, row_base) of a pass of ``rows`` rows on this rank:
+        the equal-shard values by default, ValueError for what
+        zf_condnet_forward_shard would reject."""
+        if self.world > 1 and (global_rows is None) != (row_base is None):
+            raise ValueError("under data parallelism global_rows and row_base go together: give both or neither")
+        g = rows * self.world if global_rows is None else int(global_rows)
+        b = rows * self.rank if row_base is None else int(row_base)
+        if g < rows or b < 0 or b + rows > g or (self.world == 1 and g != rows):
+            raise ValueError(f"rows [{b}, {b + rows}) of global_rows {g} (rows {rows}, world {self.world})")
+        return g, b
+
+    def forward(self, x, offsets=None, *, train: bool = True, update_stats: Optional[bool] = None, seed: int = 0,
+                global_rows: Optional[int] = None, row_base: Optional[int] = None):
         """``c`` of ``net.apply(..., train=train)`` at the trainer's
-        parameters (zf_condnet_forward): (S, features) pooled, (rows,
+        parameters (zf_condnet_forward_shard): (S, features) pooled, (rows,
         features) otherwise; a DeviceArray when ``x`` is one.  ``train=True``
         keeps the activations for one :meth:`backward`, normalises by batch
         statistics, draws the dropout mask from ``seed`` and moves the running
-        statistics when ``update_stats`` (default: ``train``)."""
+        statistics when ``update_stats`` (default: ``train``).
+
+        Data parallel: ``x`` and ``offsets`` (local to ``x``) are this rank's
+        whole sets of a global pass of ``global_rows`` element rows, of which
+        this rank's first is ``row_base`` (defaults: ``rows * world`` and
+        ``rank * rows``, equal shards; give both for any other split, see
+        :func:`shard_sets`).  The result holds this rank's sets."""
         train = bool(train)
         update_stats = train if update_stats is None else bool(update_stats)
         if update_stats and not train:
@@ -610,6 +672,7 @@ class ConditionTrainer:
         if len(shape) != 2 or shape[1] != self.in_dim:
             raise ValueError(f"x must have shape (rows, {self.in_dim}), got {tuple(shape)}")
         rows = int(shape[0])
+        global_rows, row_base = self._shard(rows, global_rows, row_base)
         if rows > self.rows_max:
             raise ValueError(f"forward takes at most rows_max = {self.rows_max} rows, got {rows}")
         off = _check_offsets_arg(offsets, rows, self._h.pooled)
@@ -618,7 +681,7 @@ class ConditionTrainer:
         xd, x_dev = _prep_x(x, self.in_dim)
         off = _device_offsets(off)
         self._pending = None
-        out = self._h.forward(xd, off, train, update_stats, seed)
+        out = self._h.forward(xd, off, train, update_stats, seed, global_rows, row_base)
         if train:
             self._pending = (out.shape[0], x_dev, rows)
         return out if x_dev else out.numpy()
@@ -702,3 +765,37 @@ class ConditionTrainer:
     def grad_tree(self, g) -> Dict[str, Any]:
         """Gradient blob -> ``params`` tree (like jax.grad's output)."""
         return self.layout.to_tree(np.asarray(g), cols=("params",))["params"]
+
+    def _n_slots(self) -> int:
+        return self.optimizer.n_slots if isinstance(self.optimizer, Chain) else 2
+
+    def opt_state(self) -> Dict[str, Any]:
+        """The optimiser's state, as ``Trainer.opt_state`` gives it:
+        ``count``, the ``learning_rate`` and ``grad_norm`` the last step used
+        (NaN before the first step; grad_norm NaN without
+        clip_by_global_norm), and ``slots``, the moment arrays as
+        ``params``-shaped trees in chain order (an ``Optimizer``: m, v)."""
+        lib = L.load_library()
+        count, lr, gn = ct.c_int64(), ct.c_double(), ct.c_double()
+        check(lib.zf_condnet_get_opt_scalars(self._h.ptr, ct.byref(count), ct.byref(lr), ct.byref(gn)),
+              "zf_condnet_get_opt_scalars")
+        slots = []
+        for k in range(self._n_slots()):
+            blob = np.empty(self.layout.size, np.float32)
+            check(lib.zf_condnet_get_opt_slot(self._h.ptr, k, blob.ctypes.data), "zf_condnet_get_opt_slot")
+            slots.append(self.layout.to_tree(blob, cols=("params",))["params"])
+        return {"count": int(count.value), "learning_rate": float(lr.value), "grad_norm": float(gn.value),
+                "slots": slots}
+
+    def load_opt_state(self, state: Dict[str, Any]) -> None:
+        """Restore what :meth:`opt_state` returned (of a trainer with the
+        same optimiser): the moments and the step counter, from which the
+        bias corrections and the schedule follow."""
+        slots = list(state["slots"])
+        if len(slots) != self._n_slots():
+            raise ValueError(f"state has {len(slots)} moment arrays, this optimiser keeps {self._n_slots()}")
+        lib = L.load_library()
+        for k, tree in enumerate(slots):
+            blob = np.ascontiguousarray(self.layout.to_blob({"params": tree}, cols=("params",)))
+            check(lib.zf_condnet_set_opt_slot(self._h.ptr, k, blob.ctypes.data), "zf_condnet_set_opt_slot")
+        check(lib.zf_condnet_set_opt_count(self._h.ptr, int(state["count"])), "zf_condnet_set_opt_count")
