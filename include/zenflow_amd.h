@@ -763,6 +763,37 @@ int zf_segment_pool_bcast(const float* gc, const int32_t* set_index, int64_t row
 int zf_segment_repeat(const float* c, int64_t sets, int F, const int64_t* off, int64_t rows, float* out,
                       int32_t* set_index, void* workspace, void* stream);
 
+/* Take whole sets by index — a minibatch of ragged sets packed on the device,
+ * what `x[np.concatenate([np.arange(off[s], off[s + 1]) for s in take])]` and
+ * a cumsum of the taken lengths do on the host (the element rows of B of S
+ * sets drawn at random, contiguous, with their CSR offsets rebuilt):
+ *   len_t          = o[take[t] + 1] - o[take[t]],  0 for take[t] outside [0, sets)
+ *   off_out[0]     = 0
+ *   off_out[t + 1] = min(off_out[t] + len_t, rows_out),         0 <= t < take_n
+ *   out[off_out[t] + j, :] = x[o[take[t]] + j, :],  j < off_out[t + 1] - off_out[t]
+ * in the set's own order, and +0 in the rows from off_out[take_n] to rows_out
+ * (rows_out below the sum of the lengths truncates: the last sets come out
+ * shortened or empty).  x: (rows, F) on the device, 0 < F <= 64; off: sets + 1
+ * int64 on the device, o its clamped form by the rule of zf_segment_sum, so
+ * any content of `off` reads inside x only; take: take_n int64 on the device,
+ * not validated but made harmless (an index outside [0, sets) is an empty
+ * set), duplicates allowed (bootstrap resampling); out: (rows_out, F);
+ * off_out: take_n + 1 int64.  Nothing at or beyond out + rows_out * F is
+ * written.
+ * off == NULL (unit mode): every set is one row, o[s] = s, sets == rows — the
+ * row gather out[t] = x[take[t]] (the per-set targets of a minibatch).
+ * workspace: zf_segment_take_workspace_bytes(sets, take_n) bytes on the
+ * device (0 for arguments the entry rejects).  One search over off_out per
+ * output row: the time does not depend on how the rows are divided into sets.
+ * No atomics: a copy, the same bits every time.  Nothing synchronises with
+ * the host; take_n == 0 or rows_out == 0 enqueue memsets only.
+ * ZF_EINVAL: NULL x / take / out / off_out / workspace, a negative count, F
+ * outside 1 .. 64, off == NULL with sets != rows; ZF_ENOTSUP: sets or take_n >
+ * 2^24, rows or rows_out > 2^31 - 1.  Nothing is enqueued then. */
+int64_t zf_segment_take_workspace_bytes(int64_t sets, int64_t take_n);
+int zf_segment_take(const float* x, int64_t rows, int F, const int64_t* off, int64_t sets, const int64_t* take,
+                    int64_t take_n, int64_t rows_out, float* out, int64_t* off_out, void* workspace, void* stream);
+
 /* Dropout — replaces nn.Dropout(rate, deterministic=not train) of Phi.__call__:
  *   keep(i, f) = u01_co(philox_at(seed, i, f, ZF_DROPOUT_STREAM).v[ZF_DROPOUT_WORD]) >= rate
  * with i the element row, f the column, Philox4x32-10 and u01_co (top 24

@@ -225,6 +225,8 @@ SIGNATURES = {
     "zf_segment_pool": (_int, [_vp, _i64, _int, _vp, _i64, _int, C.c_float, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zf_segment_pool_bcast": (_int, [_vp, _vp, _i64, _int, _i64, _int, C.c_float, _u64, _vp, _vp, _vp, _vp, _vp]),
     "zf_segment_repeat": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "zf_segment_take_workspace_bytes": (_i64, [_i64, _i64]),
+    "zf_segment_take": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "zf_condnet_backward_input": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "zf_condnet_plan": (_int, [C.POINTER(ZfCondnetDesc), C.POINTER(_i64)]),
     "zf_condnet_create": (_int, [C.POINTER(ZfCondnetDesc), _vp, _i64, _vp, _i64, _i64, _vp, C.POINTER(_vp)]),
@@ -439,6 +441,18 @@ class DeviceArray:
     def copy_from(self, other: "DeviceArray") -> None:
         assert other.nbytes == self.nbytes
         check(load_library().zf_memcpy_dtod(self.ptr, other.ptr, self.nbytes, stream()), "dtod")
+
+    def rows(self, lo: int, hi: int) -> "DeviceArray":
+        """Rows ``[lo, hi)`` as a DeviceArray on the same memory (no copy; the
+        view keeps this array alive) — a batch of a resident array."""
+        lo, hi = int(lo), int(hi)
+        if not (self.ndim >= 1 and 0 <= lo <= hi <= self.shape[0]):
+            raise ValueError(f"rows [{lo}, {hi}) of a DeviceArray of shape {self.shape}")
+        v = DeviceArray.__new__(DeviceArray)
+        row = int(np.prod(self.shape[1:], dtype=np.int64)) * self.dtype.itemsize
+        v.ptr, v.shape, v.dtype = self.ptr + lo * row, (hi - lo,) + self.shape[1:], self.dtype
+        v.nbytes, v._fin = (hi - lo) * row, self
+        return v
 
     def zero_(self) -> "DeviceArray":
         check(load_library().zf_memset_async(self.ptr, 0, self.nbytes, stream()), "memset")

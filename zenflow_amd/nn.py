@@ -34,7 +34,9 @@ second network ``rho``, ``NNBlock(1, 3, 128)``, behind the pooled sum; it is
 :func:`segment_repeat` is ``jnp.repeat(c, sizes, axis=0)`` of
 ``DeepSetFlow.sample`` on the device, :func:`segment_sum` its reverse;
 :func:`segment_mean` and :func:`segment_max` are the other two poolings on
-their own.
+their own.  :func:`segment_take` packs the element rows of a minibatch of
+sets out of a resident data set and :func:`take_rows` their per-set targets
+(``zenflow_amd.train.train_sets`` is the loop over them).
 
 No JAX is at hand here, so flax.linen's BatchNorm, Dense and Dropout are
 restated from their published definitions, as the couplings' layers are;
@@ -55,8 +57,8 @@ from .activations import act_code, swish
 from .module import Module, lecun_normal, scope_for
 from .optim import Chain
 
-__all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "clamp_offsets", "dropout_keep", "segment_max",
-           "segment_mean", "segment_repeat", "segment_sum", "shard_sets"]
+__all__ = ["ConditionNet", "ConditionTrainer", "check_offsets", "check_take", "clamp_offsets", "dropout_keep",
+           "segment_max", "segment_mean", "segment_repeat", "segment_sum", "segment_take", "shard_sets", "take_rows"]
 
 _U64 = (1 << 64) - 1
 _POOLS = {None: L.ZF_POOL_NONE, "sum": L.ZF_POOL_SUM, "max": L.ZF_POOL_MAX}
@@ -263,6 +265,106 @@ def segment_max(h, offsets):
     does, a zero row for an empty set.  Arguments and conventions as
     :func:`segment_sum`'s."""
     return _segment_pool(h, offsets, L.ZF_POOL_MAX)
+
+
+def check_take(take, sets: int) -> np.ndarray:
+    """Host set indices as int64, validated: 1-D integers, each in
+    [0, sets).  (Indices already on the device are not read back: the kernel
+    makes an index outside that range an empty set.)"""
+    a = np.asarray(take)
+    if a.ndim != 1:
+        raise ValueError(f"take must be 1-D, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        if a.dtype == object or not np.issubdtype(a.dtype, np.number) or not np.all(a == np.floor(a)):
+            raise ValueError("take must be integers")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= sets):
+        raise ValueError(f"take must lie in [0, {sets}), got {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a)
+
+
+def _take_arg(take, sets: int):
+    """A device ``take`` as it is (1-D int64), a host one validated."""
+    if isinstance(take, DeviceArray):
+        if take.ndim != 1 or take.dtype != np.int64:
+            raise ValueError(f"a device take must be 1-D int64, got {take.dtype} {take.shape}")
+        return take
+    return check_take(take, sets)
+
+
+def _take_launch(xd: DeviceArray, rows: int, F: int, od: Optional[DeviceArray], S: int, take, rows_out: int,
+                 out_shape) -> Tuple[DeviceArray, DeviceArray]:
+    """zf_segment_take on device buffers: (out, off_out)."""
+    lib = L.load_library()
+    td = take if isinstance(take, DeviceArray) else DeviceArray.from_numpy(take)
+    n = int(td.shape[0])
+    out, off_out = DeviceArray(out_shape), DeviceArray((n + 1,), np.int64)
+    ws = DeviceArray((max(1, lib.zf_segment_take_workspace_bytes(S, n)),), np.uint8)
+    check(lib.zf_segment_take(xd.ptr, rows, F, None if od is None else od.ptr, S, td.ptr, n, rows_out, out.ptr,
+                              off_out.ptr, ws.ptr, L.stream()), "zf_segment_take")
+    return out, off_out
+
+
+def segment_take(x, offsets, take, *, rows: Optional[int] = None):
+    """The sets ``take`` of a ragged batch, packed (zf_segment_take): ``x``
+    (rows_x, F <= 64) and S + 1 ``offsets`` -> ``(x_out, offsets_out)`` with
+    the element rows of set ``take[0]``, then of ``take[1]``, ... each in its
+    own order, and their ``len(take) + 1`` CSR offsets — a minibatch of a
+    deep-set data set that stays on the device.  Duplicates are allowed.
+
+    ``x_out`` has ``rows`` rows, zeros behind the last set; ``rows`` defaults
+    to the sum of the taken lengths when ``offsets`` and ``take`` are both on
+    the host.  Host offsets are validated (:func:`check_offsets`), a host
+    ``take`` too (1-D integers in [0, S)), and ``rows`` below the sum of their
+    lengths is a ValueError.  Device ``offsets`` or a device ``take`` (int64
+    DeviceArrays) are not read back: they need ``rows``, the kernel clamps the
+    offsets (:func:`clamp_offsets`), takes an index outside [0, S) as an empty
+    set and truncates at ``rows``.  Host array in, host arrays out; a
+    DeviceArray ``x`` gives DeviceArrays (``offsets_out`` int64)."""
+    rows_x, F = _shape2(x, "x")
+    off = _segment_offsets(offsets, None, rows_x)
+    S = off.shape[0] - 1
+    take = _take_arg(take, S)
+    on_host = not isinstance(off, DeviceArray) and not isinstance(take, DeviceArray)
+    if rows is None and not on_host:
+        raise ValueError("device offsets and a device take are not read back: give rows")
+    if rows is not None and int(rows) < 0:
+        raise ValueError(f"rows must not be negative, got {rows}")
+    if on_host:
+        need = int(np.diff(off)[take].sum())
+        rows = need if rows is None else int(rows)
+        if rows < need:
+            raise ValueError(f"the taken sets have {need} rows, rows = {rows}")
+    rows = int(rows)
+    L.ensure_device()
+    out, off_out = _take_launch(_to_device2(x), rows_x, F, _device_offsets(off), S, take, rows, (rows, F))
+    return (out, off_out) if isinstance(x, DeviceArray) else (out.numpy(), off_out.numpy())
+
+
+def take_rows(y, take):
+    """``y[take]`` on the device (zf_segment_take with every row its own
+    set): ``y`` (S, F <= 64), or 1-D (S,), returned 1-D — the per-set targets
+    of the minibatch that :func:`segment_take` packs.  A host ``take`` is
+    validated (1-D integers in [0, S)), a device one (int64 DeviceArray) made
+    harmless by the kernel: an index outside [0, S) is an empty set, as in
+    :func:`segment_take` — its row is left out, the rows behind it move up
+    and zero rows close the result.  Host array in, host array out;
+    DeviceArray in, DeviceArray out."""
+    if isinstance(y, DeviceArray):
+        if y.ndim not in (1, 2) or y.dtype != np.float32:
+            raise ValueError(f"y must be a 1-D or 2-D float32 DeviceArray, got {y.dtype} {y.shape}")
+        shape = y.shape
+    else:
+        shape = np.shape(y)
+        if len(shape) not in (1, 2):
+            raise ValueError(f"y must be 1-D or 2-D, got {shape}")
+    S, F = int(shape[0]), int(shape[1]) if len(shape) == 2 else 1
+    take = _take_arg(take, S)
+    n = int(take.shape[0])
+    L.ensure_device()
+    yd = y if isinstance(y, DeviceArray) else DeviceArray.from_numpy(np.ascontiguousarray(np.asarray(y, np.float32)))
+    out, _ = _take_launch(yd, S, F, None, S, take, n, (n, F) if len(shape) == 2 else (n,))
+    return out if isinstance(y, DeviceArray) else out.numpy()
 
 
 class _Layout:

@@ -700,3 +700,223 @@ def train(
             if not np.min(loss_test[-patience:]) < np.min(loss_test[-2 * patience : -patience]):
                 break
     return best_variables, best_epoch, loss_train, loss_test
+
+
+# ---------------------------------------------------------------------------
+# Deep-set flows: ragged minibatches of a resident data set
+# ---------------------------------------------------------------------------
+
+
+def plan_set_batches(offsets, batch_sets: int, world: int = 1) -> Tuple[List[int], int, int]:
+    """``(sizes, sets_max, rows_max)`` of an epoch of :func:`train_sets` over
+    the S sets of ``offsets`` (S + 1, validated): the sets per batch
+    (``batch_sets``, the last one ``S % batch_sets`` when that is not 0), and
+    the capacities of one rank's trainers — a rank's shard of a batch has at
+    most ``sets_max = ceil(min(batch_sets, S) / world)`` sets
+    (``dist.shard_rows``), and no ``sets_max`` sets have more element rows
+    than the ``sets_max`` longest ones, ``rows_max`` (at least 1): bounds no
+    batch of no permutation exceeds, so nothing is re-created during a run.
+
+    ValueError: ``batch_sets < 1``; a batch with fewer sets than ranks; and
+    empty sets enough to fill the smallest shard (a shard without an element
+    row is rejected up front, not handled)."""
+    from .nn import check_offsets
+
+    off = check_offsets(offsets, np.iinfo(np.int64).max)
+    S, batch_sets, world = off.size - 1, int(batch_sets), int(world)
+    if batch_sets < 1:
+        raise ValueError(f"batch_sets must be at least 1, got {batch_sets}")
+    if world < 1:
+        raise ValueError(f"world must be at least 1, got {world}")
+    if S < 1:
+        raise ValueError("train_sets needs at least one set")
+    sizes = [min(batch_sets, S - k) for k in range(0, S, batch_sets)]
+    if min(sizes) < world:
+        raise ValueError(f"S = {S} sets in batches of batch_sets = {batch_sets} leave a batch of {min(sizes)} sets "
+                         f"for world = {world} ranks: every batch needs at least one set per rank")
+    lengths = np.diff(off)
+    smallest = min(sizes) // world  # the fewest sets a rank's shard can have
+    empty = int((lengths == 0).sum())
+    if empty >= smallest:
+        raise ValueError(f"{empty} empty sets could fill a rank's shard of {smallest} sets (S = {S}, batch_sets = "
+                         f"{batch_sets}, world = {world}): a shard without element rows is not supported")
+    sets_max = -(-sizes[0] // world)
+    rows_max = max(1, int(np.sort(lengths)[::-1][:sets_max].sum()))
+    return sizes, sets_max, rows_max
+
+
+def _sets_arrays(X, offsets, Y, what: str):
+    """One split's (X, offsets, Y) as float32 / int64 / float32 host arrays, checked."""
+    from .nn import check_offsets
+
+    X = np.asarray(X, np.float32)
+    Y = np.asarray(Y, np.float32)
+    if X.ndim != 2:
+        raise ValueError(f"X_{what} must be 2-D (rows, in_dim), got {X.shape}")
+    if Y.ndim != 2:
+        raise ValueError(f"Y_{what} must be 2-D (sets, D), got {Y.shape}")
+    off = check_offsets(offsets, X.shape[0])
+    if Y.shape[0] != off.size - 1:
+        raise ValueError(f"Y_{what} has {Y.shape[0]} rows for the {off.size - 1} sets of offsets_{what}")
+    return np.ascontiguousarray(X), off, np.ascontiguousarray(Y)
+
+
+def _metric_sets(flow, phi, variables, X, off, Y) -> float:
+    """metric_fn of a deep-set flow, through the modules: ``c = phi(x)`` in
+    eval mode, then the float64 NLL of ``flow.apply(fv, Y, c)``."""
+    c = phi.apply(variables["phi"], X, off)
+    return _metric(flow, variables["flow"], Y, c)
+
+
+def train_sets(
+    flow,
+    phi,
+    X_train,
+    offsets_train,
+    Y_train,
+    X_test,
+    offsets_test,
+    Y_test,
+    *,
+    epochs: int = 1000,
+    batch_sets: int = 1024,
+    optimizer: Union[Optimizer, Chain, None] = None,
+    phi_optimizer: Union[Optimizer, Chain, None] = None,
+    patience: float = 0.05,
+    warmup: float = 0.2,
+    seed: int = 0,
+    progress: bool = True,
+    initial_variables=None,
+    comm=None,
+) -> Tuple[Dict[str, Any], int, List[float], List[float]]:
+    """:func:`train` for a deep-set flow (examples/deep_set.ipynb,
+    ``DeepSetFlow`` / ``loss_fn_2``): ``flow`` models ``Y`` (one row per set)
+    under the condition ``c = phi(x)``, ``phi`` a pooled ``nn.ConditionNet``
+    over the set's element rows ``X`` (``offsets``: the S + 1 CSR offsets),
+    and both are trained jointly on random minibatches of ``batch_sets`` sets.
+    Returns ``(best_variables, best_epoch, loss_train, loss_test)`` with
+    ``variables = {"flow": ..., "phi": ...}``; epochs, permutation
+    (``default_rng([seed, epoch])``), metrics (eval mode: the last batch, the
+    test sets), ``best_epoch`` and the ``warmup`` / ``patience`` early stopping
+    are :func:`train`'s.
+
+    The training data is uploaded once and stays resident; every batch is
+    packed on the device (``nn.segment_take``, ``nn.take_rows``), so that a
+    step is
+
+        xb, ob = nn.segment_take(Xd, off_d, take_b, rows=rows_b)
+        yb     = nn.take_rows(Yd, take_b)
+        c      = ct.forward(xb, ob, seed=seed * 2**32 + step)
+        gc     = tr.step(yb, c, cond_grad=True)
+        ct.step(gc)
+
+    with ``take_b`` the batch's slice of the epoch's permutation, ``rows_b``
+    its element rows (from the host offsets) and ``step`` the optimiser steps
+    taken so far.  One ``Trainer`` and one ``nn.ConditionTrainer`` serve the
+    run, sized by :func:`plan_set_batches`.
+
+    ``initial_variables=None``: the flow is initialised as :func:`train` does
+    (with a zero ``(1, phi.features)`` condition), ``phi`` with
+    ``phi.init(seed + 1, X_train, offsets_train)``.  ``optimizer`` /
+    ``phi_optimizer``: the flow's / ``phi``'s, an :class:`Optimizer` or a
+    ``zenflow_amd.optim`` chain each (default nadamw(1e-3)).
+
+    ``comm`` (as :func:`train` takes it, every rank calling with the same data
+    and seed): a batch's sets are cut contiguously over the ranks
+    (``dist.shard_rows``), each rank gathers and passes its own sets
+    (``global_rows`` / ``row_base`` of ``ConditionTrainer.forward``), and every
+    rank evaluates the metrics on all of the data, so all ranks return
+    identical results.  Their bits are not one device's: random ragged shards
+    do not have equal element rows.
+
+    Checked on the host before any device call (ValueError): shapes, offsets,
+    one ``Y`` row per set, ``batch_sets >= 1``, a ``phi`` without pooling, a
+    batch (the short last one included) with fewer sets than ranks, and
+    enough empty sets to leave a rank's shard without an element row
+    (rejected, not handled; see :func:`plan_set_batches`)."""
+    from . import nn
+
+    if warmup < 1:
+        warmup = warmup * epochs
+    warmup = int(warmup)
+    if patience < 1:
+        patience = patience * epochs
+    patience = int(patience)
+
+    if not isinstance(phi, nn.ConditionNet) or phi.pool is None:
+        raise ValueError("phi must be a pooled nn.ConditionNet (pool='sum' or 'max'): one condition row per set")
+    X_train, off_train, Y_train = _sets_arrays(X_train, offsets_train, Y_train, "train")
+    X_test, off_test, Y_test = _sets_arrays(X_test, offsets_test, Y_test, "test")
+    in_dim, D, Cd = X_train.shape[1], Y_train.shape[1], phi.features
+    if X_test.shape[1] != in_dim or Y_test.shape[1] != D:
+        raise ValueError(f"the test split has {X_test.shape[1]} element and {Y_test.shape[1]} target columns, the "
+                         f"train split {in_dim} and {D}")
+    world = 1 if comm is None else int(comm.world)
+    rank = 0 if comm is None else int(comm.rank)
+    sizes, sets_max, rows_max = plan_set_batches(off_train, batch_sets, world)
+    batch_sets = int(batch_sets)
+    S = off_train.size - 1
+
+    if initial_variables is None:
+        variables = {"flow": flow.init(PRNGKey(seed), Y_train[:1], np.zeros((1, Cd), np.float32)),
+                     "phi": phi.init(seed + 1, X_train, off_train)}
+    else:
+        variables = initial_variables
+    tr = Trainer(flow, variables["flow"], D, Cd, sets_max, optimizer, comm=comm)
+    ct = nn.ConditionTrainer(phi, variables["phi"], in_dim, rows_max, sets_max=sets_max, optimizer=phi_optimizer,
+                             comm=comm if world > 1 else None)
+    Xd, off_d, Yd = DeviceArray.from_numpy(X_train), DeviceArray.from_numpy(off_train), DeviceArray.from_numpy(Y_train)
+    Xt, off_t, Yt = DeviceArray.from_numpy(X_test), DeviceArray.from_numpy(off_test), DeviceArray.from_numpy(Y_test)
+    lengths = np.diff(off_train)
+
+    loop = range(epochs)
+    if progress:
+        try:
+            from tqdm import tqdm
+
+            loop = tqdm(loop)
+        except ModuleNotFoundError:  # pragma: no cover
+            pass
+
+    loss_train: List[float] = []
+    loss_test: List[float] = []
+    best_epoch = 0
+    best_variables = variables
+    step = 0
+    for epoch in loop:
+        perm = np.random.default_rng([seed, epoch]).permutation(S)
+        take_d = DeviceArray.from_numpy(perm.astype(np.int64))  # one upload per epoch
+        first = 0
+        for n in sizes:
+            lo, hi = shard_rows(n, rank, world)
+            len_b = lengths[perm[first : first + n]]
+            take_b = take_d.rows(first + lo, first + hi)
+            xb, ob = nn.segment_take(Xd, off_d, take_b, rows=int(len_b[lo:hi].sum()))
+            yb = nn.take_rows(Yd, take_b)
+            shard = {} if world == 1 else {"global_rows": int(len_b.sum()), "row_base": int(len_b[:lo].sum())}
+            c = ct.forward(xb, ob, seed=seed * 2**32 + step, **shard)
+            gc = tr.step(yb, c, global_rows=n, cond_grad=True)
+            ct.step(gc)
+            step += 1
+            first += n
+        # the last batch, all of it on every rank
+        last = take_d.rows(S - sizes[-1], S)
+        xb, ob = nn.segment_take(Xd, off_d, last, rows=int(lengths[perm[S - sizes[-1] :]].sum()))
+        yb = nn.take_rows(Yd, last)
+
+        variables = {"flow": tr.variables(), "phi": ct.variables()}
+        loss_train.append(_metric_sets(flow, phi, variables, xb, ob, yb))  # last batch, as train.py:122
+        loss_test.append(_metric_sets(flow, phi, variables, Xt, off_t, Yt))
+
+        if not np.isfinite(loss_train[-1]):
+            warnings.warn(f"epoch {epoch}: loss[train] not finite, abort training", RuntimeWarning)
+            break
+
+        if loss_test[-1] <= loss_test[best_epoch]:
+            best_epoch = epoch
+            best_variables = variables
+
+        if epoch >= warmup and epoch >= 2 * patience and epoch % patience == 0:
+            if not np.min(loss_test[-patience:]) < np.min(loss_test[-2 * patience : -patience]):
+                break
+    return best_variables, best_epoch, loss_train, loss_test
